@@ -15,12 +15,18 @@ SH3, background path: bg = 0, then composite with a (H, W, 3) background image +
 64-view MVDream-style orbit batch
 (4 elevations x 16 azimuths), views sharded across ranks (strong scaling: the 64-view batch is fixed).
 
-Single GPU:  python bench.py [--steps K --warmup W]
+Single GPU:  python bench.py [--steps K --warmup W] [--dump-outputs DIR] [--full]
 N GPUs:      python bench.py --gpus N ...   (starts N ranks itself through torch.distributed.run), or
              python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
                  --master-port P bench.py --gpus N --steps K --warmup W
---gpus must equal the launched world size.  Rank 0 prints one JSON line; at N = 1 it carries the C5 (SuGaR
-normal renderer) and 8-view-set lines as sub-objects (--extra-lines).
+--gpus must equal the launched world size.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (with the phase timings and
+roofline fields of those same steps).  --full adds everything that takes runs of its own: at N = 1 the C5 (SuGaR
+normal renderer) and 8-view-set lines as sub-objects (--extra-lines), the per-view drop-in path, the distCUDA2
+timing and the CPU baseline; at N > 1 the overlapped-gather variant of the step.
+--dump-outputs DIR writes what the last timed step returned to its caller (the rendered maps and the parameter
+gradients; seeded inputs, so two builds can be compared output for output) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -31,6 +37,7 @@ import os
 import platform
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "threestudio-3dgs_amd"))
@@ -55,6 +62,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the measurements that take runs of their own: --extra-lines, "
+                         "the per-view path, distCUDA2 and the CPU baseline (N = 1), the overlapped-gather variant "
+                         "(N > 1); without it those options have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rendered maps, parameter gradients) as "
+                         "DIR/<name>.npy, float32; arrays above 2^20 elements as a fixed seeded sample")
     ap.add_argument("--gaussians", type=int, default=1_000_000)
     ap.add_argument("--res", type=int, default=1024)
     ap.add_argument("--views", type=int, default=64, help="global views per step (sharded over ranks)")
@@ -100,7 +114,10 @@ def parse():
     ap.add_argument("--per-view-views", type=int, default=16,
                     help="views of the drop-in per-view path (one GaussianRasterizer call per view, the "
                          "reference's loop) timed after the headline, reported beside it (0 = skip)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def log(*a):
@@ -205,6 +222,7 @@ SUGAR_SEPARATE = os.environ.get("GSR_BENCH_SUGAR_SEPARATE") == "1"  # C5: two se
 SHADE_KA, SHADE_KD = (0.1, 0.1, 0.1), (0.9, 0.9, 0.9)  # the material's default ambient / diffuse colours
 
 
+CAPTURE = None  # a dict while the step whose outputs --dump-outputs writes runs: render_views* leave their means2D in it
 GRAD_REDUCE = None  # view_shard.ChunkedGradReduce when the reduction is overlapped with the backward (N > 1)
 FUSED_CLAMP = True  # C5: the renderer's clamp formed in the blends (--fused-clamp)
 
@@ -217,6 +235,8 @@ def render_views(rep: Replica, settings, bg_img, shade=None):
     from diff_gaussian_rasterization.composite import composite_background
 
     m2 = placeholders(rep, len(settings))
+    if CAPTURE is not None:
+        CAPTURE["means2D"] = m2
     if shade is not None:
         from diff_gaussian_rasterization.shading import shade_views
 
@@ -250,6 +270,8 @@ def render_views_sugar(rep: Replica, settings, shade):
     P = rep.means3D.shape[0]
     dev = rep.means3D.device
     m2 = placeholders(rep, len(settings))
+    if CAPTURE is not None:
+        CAPTURE["means2D"] = m2
     # pass 1 colours: SuGaRModel.get_points_rgb() = SH2RGB of the DC coefficients, passed as override_color
     # (system/sugar_static.py:117-121, geometry/sugar.py:650-660)
     colors = rep.shs[:, 0, :] * SH_C0 + 0.5
@@ -273,6 +295,52 @@ def render_views_sugar(rep: Replica, settings, shade):
     nmap = sugar_normal_map(normal, alpha)  # normalize, flip x / y, alpha-weighted map, alpha > 0.99 mask (fused)
     depth = torch.where(alpha > 0.99, depth, depth.detach())
     return color, depth, alpha, nmap, nmap_dist
+
+
+DUMP_CAP = 1 << 20  # elements per dumped array (4 MB as float32); at most 14 arrays, so under 64 MB in all
+
+
+def _sample_index(name, n, k):
+    """k sorted indices into range(n), fixed by the array's name (the same for every run and build)."""
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    return np.sort(rng.integers(0, n, size=k))
+
+
+def dump_outputs(dirpath, names, outs, rep, bg_grads, means2D):
+    """--dump-outputs: what the last timed step handed its caller, as <dirpath>/<name>.npy (float32): the output
+    maps `outs` (a tuple of (V, ...) tensors, or per view a tuple for the per-view path) under `names`, the
+    gradients of the Gaussian parameters (summed over ranks at N > 1), of the background images and of the views'
+    means2D placeholders.  An array of more than DUMP_CAP elements is written as a seeded sample of its flattened
+    elements (means2D: of the Gaussians, all views), whole otherwise."""
+    os.makedirs(dirpath, exist_ok=True)
+
+    def save(name, t):
+        t = t.detach()
+        if t.numel() > DUMP_CAP:
+            idx = torch.from_numpy(_sample_index(name, t.numel(), DUMP_CAP)).to(t.device)
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(dirpath, name + ".npy"), t.to(torch.float32).cpu().numpy())
+        log(f"[bench] dumped {name} {tuple(t.shape)}")
+
+    if isinstance(outs, list):  # per-view path: one tuple per view
+        outs = tuple(torch.stack([o[i] for o in outs]) for i in range(len(outs[0])))
+    for name, t in zip(names, outs):
+        save(name, t)
+    pnames = ["means3D", "scales", "rotations", "opacities", "shs", "normals"]
+    for name, p in zip(pnames, rep.params):
+        if p.grad is not None:
+            save("grad_" + name, p.grad)
+    bg_grads = [g for g in bg_grads if g is not None]
+    if bg_grads:
+        save("grad_background", bg_grads[0] if len(bg_grads) == 1 else torch.stack(bg_grads))
+    grads = [m.grad for m in (means2D or []) if m.grad is not None]
+    if grads:
+        P = grads[0].shape[0]
+        k = max(1, DUMP_CAP // (3 * len(grads)))
+        if P > k:
+            idx = torch.from_numpy(_sample_index("grad_means2D", P, k)).to(grads[0].device)
+            grads = [g[idx] for g in grads]
+        save("grad_means2D", torch.stack(grads))
 
 
 PROFILE_VIEWS_PER_LAUNCH = 64  # profiles/run_profiles.sh: bench.py defaults, one 64-view set per launch
@@ -624,14 +692,14 @@ def config_fields(args, world, per, comm, K_mean, L_mean, chunked_reduce):
 
 def run_workload(args, world, rank, device, comm, headline=True):
     """Build the workload of `args`, run W warm-up and K timed steps (barrier + synchronize on both sides, max
-    over ranks) and return (result dict on rank 0 else None, scene).  headline: also the per-view-path and
-    distCUDA2 lines and, for N > 1, the overlapped-gather variant of the same step."""
+    over ranks) and return (result dict on rank 0 else None, scene).  headline: --dump-outputs applies, and with
+    --full also the per-view-path and distCUDA2 lines and, for N > 1, the overlapped-gather variant of the step."""
     import gsr_synthetic as gs
     from diff_gaussian_rasterization import _C
     from diff_gaussian_rasterization.view_shard import (ChunkedGradReduce, all_gather_views, all_gather_views_async,
                                                         allreduce_grads, shard_range)
 
-    global GRAD_REDUCE, FUSED_CLAMP
+    global GRAD_REDUCE, FUSED_CLAMP, CAPTURE
     FUSED_CLAMP = args.fused_clamp == "on"
     overlap = world > 1 and args.overlap_reduce == "on" and args.path == "batched" and args.views >= world \
         and not SUGAR_SEPARATE
@@ -690,7 +758,11 @@ def run_workload(args, world, rank, device, comm, headline=True):
             full = all_gather_views(img, args.views)
             return full
 
-    def step():
+    def step(keep=False):
+        # keep: the step whose outputs --dump-outputs writes; it holds on to what it returned and its gradients
+        # (references only) instead of dropping them
+        global CAPTURE
+        CAPTURE = {} if keep else None
         if args.workload == "sugar":
             outs = render_views_sugar(rep, settings, shade)
             if world > 1:
@@ -723,18 +795,21 @@ def run_workload(args, world, rank, device, comm, headline=True):
         if GRAD_REDUCE is None:
             allreduce_grads(rep.params)  # one flat RCCL all-reduce of the Gaussian parameter gradients
         # (else the rasterizer's backward summed them over ranks range by range, overlapped with it)
+        if keep:
+            CAPTURE["outs"] = outs
+            return
         rep.zero_grad()
         bg_img.grad = None
         for b in bg_views:
             b.grad = None
 
-    def timed(steps):
+    def timed(steps, keep_last=False):
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(steps):
-            step()
+        for i in range(steps):
+            step(keep=keep_last and i == steps - 1)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -754,7 +829,8 @@ def run_workload(args, world, rank, device, comm, headline=True):
     if not args.no_profile:
         _C.profile_read(reset=True)
         _C.profile_enable(True)
-    elapsed = timed(args.steps)
+    dump = headline and args.dump_outputs is not None
+    elapsed = timed(args.steps, keep_last=dump)
     phases = None
     if not args.no_profile:
         _C.profile_enable(False)
@@ -765,8 +841,22 @@ def run_workload(args, world, rank, device, comm, headline=True):
     host_trace = _C.host_trace_read() if _C.HOST_TRACE else None
     launched = _C.profile_kernels()
 
+    if dump:
+        if rank == 0:
+            if args.workload == "sugar":
+                names = ["color", "depth", "alpha", "normal_map", "normal_from_depth"]
+            else:
+                names = ["color", "depth", "alpha", "radii", "normal"]
+            dump_outputs(args.dump_outputs, names, CAPTURE["outs"], rep, [bg_img.grad] + [b.grad for b in bg_views],
+                         CAPTURE.get("means2D"))
+        CAPTURE = None
+        rep.zero_grad()
+        bg_img.grad = None
+        for b in bg_views:
+            b.grad = None
+
     variant = None
-    if headline and world > 1 and args.gather == "sync":
+    if headline and args.full and world > 1 and args.gather == "sync":
         # the same step with the image all-gather overlapped with the backward (valid when the loss decomposes
         # over views or rank-aligned view groups; reported beside the headline, never as it)
         gather_mode[0] = "overlap"
@@ -819,9 +909,9 @@ def run_workload(args, world, rank, device, comm, headline=True):
         res["gap_ms_per_step"] = round(1000.0 * elapsed / args.steps - sum(ms for ms, _ in phases.values()) /
                                        args.steps, 3)
         res.update(roofline_fields(args, phases, Ks, Ls, H, W, launched, build=_C.build_id()))
-    if headline and not args.no_knn:
+    if headline and args.full and not args.no_knn:
         res["init_knn"] = time_knn(rep.means3D.detach())
-    if headline and world == 1 and args.per_view_views > 0 and args.workload == "c3" \
+    if headline and args.full and world == 1 and args.per_view_views > 0 and args.workload == "c3" \
             and args.epilogue == "background" and args.path == "batched":
         res["per_view_path"] = time_per_view_path(rep, mine, bg_zero, bg_img, upstream, args.per_view_views)
     return res, scene
@@ -872,7 +962,7 @@ def main():
     default_c3 = (args.workload == "c3" and args.epilogue == "background" and args.path == "batched"
                   and args.res == 1024 and args.gaussians == 1_000_000 and args.views == 64)
     extra = [] if args.extra_lines == "none" else args.extra_lines.split(",")
-    if world == 1 and default_c3 and extra:
+    if args.full and world == 1 and default_c3 and extra:
         c3_scene = scene
         for name in extra:
             sub = argparse.Namespace(**vars(args))
@@ -890,7 +980,7 @@ def main():
             torch.cuda.empty_cache()
             res[name] = compact(r)
         scene = c3_scene
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline(scene, args.res, args.cpu_views)
         rnd = lambda v: round(v, 5) if isinstance(v, float) else v  # noqa: E731
         res["cpu_baseline"] = {k: ({kk: rnd(vv) for kk, vv in v.items()} if isinstance(v, dict) else rnd(v))

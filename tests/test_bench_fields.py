@@ -167,6 +167,68 @@ def test_product_timing_imports_no_test_code():
     assert src.count("import oracle") == 1
 
 
+def test_plain_run_is_the_default_and_steps_are_positive():
+    """A plain run measures the headline only: --full (the secondary lines, the per-view path, distCUDA2, the CPU
+    baseline) and --dump-outputs are off unless asked for; --steps is the number of timed steps, at least 1."""
+    import pytest
+
+    a = _args("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    assert _args("--full").full is True and _args("--dump-outputs", "d").dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        _args("--steps", "0")
+
+
+def test_dump_outputs_writes_seeded_float32_arrays(tmp_path):
+    """--dump-outputs: every array a caller of the step receives as <name>.npy in float32; an array above
+    bench.DUMP_CAP elements as a sample at indices fixed by its name, the same from run to run; the means2D
+    gradients sampled over the Gaussians for all views."""
+    import types
+
+    import numpy as np
+    import torch
+
+    g = torch.Generator().manual_seed(0)
+    V, P = 2, 200_000
+    big = torch.randn((V, 3, 600, 300), generator=g)  # 1 080 000 elements > DUMP_CAP
+    assert big.numel() > bench.DUMP_CAP
+    outs = (big, torch.randn((V, 1, 8, 8), generator=g), torch.rand((V, 1, 8, 8), generator=g),
+            torch.arange(V * 5, dtype=torch.int32).reshape(V, 5))
+    params = []
+    for shape in ((P, 3), (P, 3), (P, 4), (P, 1), (P, 16, 3)):
+        p = torch.zeros(shape, requires_grad=True)
+        p.grad = torch.randn(shape, generator=g)
+        params.append(p)
+    params[3].grad = None  # a parameter without a gradient is left out
+    rep = types.SimpleNamespace(params=params)
+    m2 = [torch.zeros((P, 3), requires_grad=True) for _ in range(V)]
+    for m in m2:
+        m.grad = torch.randn((P, 3), generator=g)
+    bg = torch.randn((V, 8, 8, 3), generator=g)
+    names = ["color", "depth", "alpha", "radii", "normal"]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), names, outs, rep, [bg], m2)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(n + ".npy" for n in ("color", "depth", "alpha", "radii", "grad_means3D", "grad_scales",
+                                                "grad_rotations", "grad_shs", "grad_background", "grad_means2D"))
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and a.size <= bench.DUMP_CAP and np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= 64 * 2 ** 20
+    color = np.load(tmp_path / "a" / "color.npy")
+    idx = bench._sample_index("color", big.numel(), bench.DUMP_CAP)
+    assert color.shape == (bench.DUMP_CAP,) and np.array_equal(color, big.reshape(-1).numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "depth.npy"), outs[1].numpy())  # small arrays whole, in shape
+    assert np.array_equal(np.load(tmp_path / "a" / "radii.npy"), outs[3].numpy().astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "grad_means3D.npy"), params[0].grad.numpy())
+    k = bench.DUMP_CAP // (3 * V)
+    gi = bench._sample_index("grad_means2D", P, k)
+    assert np.array_equal(np.load(tmp_path / "a" / "grad_means2D.npy"),
+                          np.stack([m.grad.numpy()[gi] for m in m2]))
+
+
 def test_pairs_of_the_diag_build_of_the_same_sources_are_used(tmp_path):
     """the diagnostic library's id is the product's id + "-diag" (csrc/Makefile); its pair counts are
     accepted for the product of the same sources, another build's are not."""
