@@ -63,8 +63,9 @@ const char* gsr_version(void);
  *      gsr_profile_kernel (the blend kernels the phases ran).
  *   5  gsr_sort_work_bytes / gsr_sort_pairs / gsr_sort_rank_mode (the library's sort, for tests);
  *      gsr_set_preprocess_ex (the two-colour render's second colours written into the records).
+ *   6  gsr_knn_points_workspace_bytes / gsr_knn_points (the K nearest neighbours with indices).
  */
-#define GSR_ABI_VERSION 5
+#define GSR_ABI_VERSION 6
 int gsr_abi_version(void);
 /* Message of the last failing call on this thread ("" if none). */
 const char* gsr_last_error(void);
@@ -420,6 +421,22 @@ int gsr_shade_views_backward(int V, int height, int width, int flags, const int*
 size_t gsr_knn_workspace_bytes(int P);
 int gsr_knn_mean_dist(int P, const float* points, float* mean_dist, void* workspace, size_t workspace_bytes,
                       void* stream);
+
+/*
+ * The K nearest points of each of P points within the same cloud, (P, 3) -> dists (P, K) float, idx (P, K) int64:
+ * replaces pytorch3d.ops.knn_points(points[None], points[None], K) of the SuGaR geometry and regulariser
+ * (geometry/sugar.py:646, utils/sugar_utils.py:41,248).  1 <= K <= GSR_KNN_MAX_K.  Exact search over the tree of
+ * gsr_knn_mean_dist with the same per-pair fp32 squared distance fma(dz, dz, fma(dy, dy, dx * dx)).  A point is its own
+ * neighbour (distance 0).  Each row ascends by (distance, index): exact fp32 ties go to the lower input index, so
+ * the result is a pure function of the input.  Rows of a cloud with P < K end with dists = +inf, idx = -1 in the
+ * missing columns.  NaN or infinite coordinates: unspecified.  Indices refer to the input order and are written as
+ * int64 directly.  workspace: gsr_knn_points_workspace_bytes(P, K) bytes of device memory (256-B aligned).  Kernels
+ * run on `stream`; the library allocates nothing.  P = 0 launches nothing.
+ */
+#define GSR_KNN_MAX_K 32
+size_t gsr_knn_points_workspace_bytes(int P, int K);
+int gsr_knn_points(int P, int K, const float* points, float* dists, long long* idx, void* workspace,
+                   size_t workspace_bytes, void* stream);
 
 /*
  * The view-segmented stable LSD radix sort that every sort of this library runs (the depth sort, the tile sort and

@@ -488,6 +488,26 @@ int gsr_knn_mean_dist(int P, const float* points, float* mean_dist, void* worksp
   return last_launch();
 }
 
+size_t gsr_knn_points_workspace_bytes(int P, int K) {
+  (void)K;  // the lists live in registers: the tree is all the workspace holds
+  return knn_workspace_bytes(P < 0 ? 0 : P);
+}
+
+int gsr_knn_points(int P, int K, const float* points, float* dists, long long* idx, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+  if (K < 1 || K > GSR_KNN_MAX_K) return fail(GSR_EINVAL, "%s", "K must be in 1..32");
+  if (P < 0) return fail(GSR_EINVAL, "%s", "negative point count");
+  if (P == 0) {  // nothing to launch, no device touched
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (points == nullptr || dists == nullptr || idx == nullptr || workspace == nullptr)
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (workspace_bytes < knn_workspace_bytes(P)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_knn_points(P, K, points, dists, idx, workspace, (hipStream_t)stream);
+  return last_launch();
+}
+
 // ---- the view-segmented radix sort (tests: every sort of the library runs seg_sort) -----------------
 struct SortWork {
   uint32_t *keys2, *vals2, *counts, *totals;

@@ -225,6 +225,10 @@ void launch_shade_bwd(const ShadeArgs& A, const ShadeGrads& G, hipStream_t strea
 // 3-NN mean squared distance (simple_knn.distCUDA2) — gsr_knn.hip.
 size_t knn_workspace_bytes(int P);
 int launch_knn_mean_dist(int P, const float* points, float* out, void* workspace, hipStream_t stream);
+// The K (1..32) nearest points of every point, itself included (pytorch3d.ops.knn_points of a cloud against itself):
+// the same tree and workspace; dists / idx are (P, K), rows ascending by (squared distance, input index).
+int launch_knn_points(int P, int K, const float* points, float* dists, long long* idx, void* workspace,
+                      hipStream_t stream);
 void launch_gauss_backward(const GaussBackwardArgs& a, ViewGradArgs va, const AccumArgs& b, hipStream_t stream);
 
 }  // namespace gsr

@@ -27,6 +27,11 @@
 //      in |dx|, |dy|, |dz|, so no box holding a closer point is skipped.
 //   5. results are written back to the input order.
 // HBM traffic is small (≈ 12 B read + 4 B written per point plus the sort); the query is VALU-bound.
+//
+// knn_points (replaces pytorch3d.ops.knn_points of a cloud against itself: the SuGaR geometry's reset_neighbors,
+// geometry/sugar.py:646, utils/sugar_utils.py:41,248) runs steps 1-3 unchanged and the same walk with another
+// per-lane list: the K <= 32 nearest points, the point itself included, as (distance, input index) pairs sorted
+// by (distance, index), written to (P, K) float32 / int64 rows in input order (k_knn_points).
 #include <float.h>
 
 #include "gsr_kernels.h"
@@ -227,22 +232,67 @@ __device__ __forceinline__ void knn_insert(float d, float& b0, float& b1, float&
   b0 = n0, b1 = n1, b2 = fminf(b2, c2);
 }
 
-__global__ __launch_bounds__(256) void k_knn_query(KnnQuery Q) {
-#pragma clang fp contract(off)
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  const int base = wave * 64;
-  if (base >= Q.P) return;  // uniform per wave
-  const int i = base + lane;
-  const bool valid = i < Q.P;
-  const int qi = valid ? i : base;
-  const float* qb = Q.bpts + (size_t)(qi / KNN_BOX) * 3 * KNN_BOX + (qi % KNN_BOX);
-  const float4 q = make_float4(qb[0], qb[KNN_BOX], qb[2 * KNN_BOX], 0.0f);
+// Per-lane candidate lists of the query walk (knn_walk below).  A list gives the lane's pruning bound
+// (worst(): a node or point at exactly this distance is still looked at), is told which box is scanned next
+// (begin_box) and is offered every point of that box (add: `slot` is the point's position in the box, a
+// compile-time constant after unrolling; d its squared distance to the lane's query).
+
+// distCUDA2: the 3 smallest distances to the other points.
+struct KnnTop3 {
   float b0 = FLT_MAX, b1 = FLT_MAX, b2 = FLT_MAX;
+  int i;     // the lane's sorted position
+  int self;  // position of the lane's own point in the scanned box (or outside 0..31)
+  __device__ __forceinline__ float worst() const { return b2; }
+  __device__ __forceinline__ void begin_box(int b) { self = i - b * KNN_BOX; }
+  __device__ __forceinline__ void add(int slot, float d) { knn_insert(slot == self ? FLT_MAX : d, b0, b1, b2); }
+};
+
+// knn_points: the KCAP smallest (distance, input index) pairs, the point itself included.  An entry is one signed
+// 64-bit key, distance bits << 32 | input index: distances are >= +0, so their bit patterns order like the values
+// and one integer compare orders by (distance, index).  Empty entries are (+inf, KNN_NO_INDEX); a list asked for
+// fewer than KCAP neighbours starts with KCAP - K negative keys in front, which no candidate displaces, so that
+// the K-th best is always e[KCAP - 1].  All indices into e[] are compile-time constants (registers, no scratch).
+constexpr uint32_t KNN_NO_INDEX = 0xffffffffu;
+constexpr long long KNN_EMPTY = (long long)((0x7f800000ull << 32) | KNN_NO_INDEX);
+template <int KCAP>
+struct KnnTopK {
+  long long e[KCAP];
+  bool valid;             // lanes past the last point never insert
+  int lane, P;
+  const uint32_t* order;  // sorted position -> input index
+  uint32_t ordv;          // lanes 0..31: input index of the scanned box's point `lane` (KNN_NO_INDEX: padding)
+  __device__ __forceinline__ void init(int K) {
+#pragma unroll
+    for (int k = 0; k < KCAP; ++k) e[k] = k < KCAP - K ? (long long)(k - KCAP) : KNN_EMPTY;
+  }
+  __device__ __forceinline__ float worst() const { return __uint_as_float((uint32_t)(e[KCAP - 1] >> 32)); }
+  __device__ __forceinline__ void begin_box(int b) {
+    const int pos = b * KNN_BOX + (lane & (KNN_BOX - 1));
+    ordv = pos < P ? order[pos] : KNN_NO_INDEX;  // the padding of the last box equals an empty entry: never inserted
+  }
+  __device__ __forceinline__ void add(int slot, float d) {
+    // after warm-up most points are rejected by every lane: the chain runs only when some lane inserts
+    if (__ballot(valid && d <= worst()) == 0ull) return;
+    const uint32_t id = (uint32_t)__builtin_amdgcn_readlane((int)ordv, slot);
+    const long long c = (long long)(((unsigned long long)__float_as_uint(d) << 32) | id);
+    bool lt[KCAP];  // monotone in k (the list is sorted); a lane that does not insert has none set
+#pragma unroll
+    for (int k = 0; k < KCAP; ++k) lt[k] = c < e[k];
+#pragma unroll
+    for (int k = KCAP - 1; k > 0; --k) e[k] = lt[k - 1] ? e[k - 1] : (lt[k] ? c : e[k]);
+    e[0] = lt[0] ? c : e[0];
+  }
+};
+
+// The query walk of one wave over the hierarchy (design point 4 above), shared by the query kernels: `base` is the
+// wave's first sorted position, q the lane's query point, L the lane's candidate list.
+template <class List>
+__device__ __forceinline__ void knn_walk(const KnnQuery& Q, int base, int lane, bool valid, float4 q, List& L) {
+#pragma clang fp contract(off)
   const float lim_invalid = -1.0f;  // invalid lanes never ask for a node
-  auto need = [&](float d) { return valid ? d <= b2 : d <= lim_invalid; };
+  auto need = [&](float d) { return valid ? d <= L.worst() : d <= lim_invalid; };
   // AABB of the wave's queries and the wave's loosest current bound: a node whose AABB is farther from the
-  // query AABB than sqrt(max b2) holds no lane's neighbour (conservative: exactness kept)
+  // query AABB than sqrt(max worst) holds no lane's neighbour (conservative: exactness kept)
   float ql[3] = {valid ? q.x : INFINITY, valid ? q.y : INFINITY, valid ? q.z : INFINITY};
   float qh[3] = {valid ? q.x : -INFINITY, valid ? q.y : -INFINITY, valid ? q.z : -INFINITY};
 #pragma unroll
@@ -253,7 +303,7 @@ __global__ __launch_bounds__(256) void k_knn_query(KnnQuery Q) {
     }
   }
   auto bound = [&]() {
-    float m = valid ? b2 : 0.0f;
+    float m = valid ? L.worst() : 0.0f;
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
     return m;
   };
@@ -284,7 +334,7 @@ __global__ __launch_bounds__(256) void k_knn_query(KnnQuery Q) {
   };
   auto scan_box = [&](int b) {
     if (!refine(0, b)) return;
-    const int self = i - b * KNN_BOX;  // position of the lane's own point in this box (or outside 0..31)
+    L.begin_box(b);
     const cfptr box = (cfptr)Q.bpts + (size_t)b * 3 * KNN_BOX;
 #pragma unroll
     for (int c = 0; c < KNN_BOX; c += 16) {  // 16 points = 48 SGPRs per batch of s_load_dwordx16
@@ -292,10 +342,7 @@ __global__ __launch_bounds__(256) void k_knn_query(KnnQuery Q) {
 #pragma unroll
       for (int j = 0; j < 16; ++j) xs[j] = box[c + j], ys[j] = box[KNN_BOX + c + j], zs[j] = box[2 * KNN_BOX + c + j];
 #pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const float d = dist2(xs[j] - q.x, ys[j] - q.y, zs[j] - q.z);
-        knn_insert(c + j == self ? FLT_MAX : d, b0, b1, b2);
-      }
+      for (int j = 0; j < 16; ++j) L.add(c + j, dist2(xs[j] - q.x, ys[j] - q.y, zs[j] - q.z));
     }
   };
 
@@ -333,7 +380,56 @@ __global__ __launch_bounds__(256) void k_knn_query(KnnQuery Q) {
       }
     }
   }
-  if (valid) Q.out[Q.order[i]] = (b0 + b1 + b2) / 3.0f;
+}
+
+// the wave's 64 consecutive sorted points: false (uniform) when the wave has none
+__device__ __forceinline__ bool knn_wave_query(const KnnQuery& Q, int& base, int& lane, int& i, bool& valid,
+                                               float4& q) {
+  lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  base = wave * 64;
+  if (base >= Q.P) return false;
+  i = base + lane;
+  valid = i < Q.P;
+  const int qi = valid ? i : base;
+  const float* qb = Q.bpts + (size_t)(qi / KNN_BOX) * 3 * KNN_BOX + (qi % KNN_BOX);
+  q = make_float4(qb[0], qb[KNN_BOX], qb[2 * KNN_BOX], 0.0f);
+  return true;
+}
+
+__global__ __launch_bounds__(256) void k_knn_query(KnnQuery Q) {
+  int base, lane, i;
+  bool valid;
+  float4 q;
+  if (!knn_wave_query(Q, base, lane, i, valid, q)) return;
+  KnnTop3 L;
+  L.i = i;
+  knn_walk(Q, base, lane, valid, q, L);
+  if (valid) Q.out[Q.order[i]] = (L.b0 + L.b1 + L.b2) / 3.0f;
+}
+
+// knn_points: row order[i] of dists / idx (P x K, input order) gets the lane's K best, ascending by (distance, index)
+template <int KCAP>
+__global__ __launch_bounds__(256) void k_knn_points(KnnQuery Q, int K, float* __restrict__ dists,
+                                                    long long* __restrict__ idx) {
+  int base, lane, i;
+  bool valid;
+  float4 q;
+  if (!knn_wave_query(Q, base, lane, i, valid, q)) return;
+  KnnTopK<KCAP> L;
+  L.valid = valid, L.lane = lane, L.P = Q.P, L.order = Q.order;
+  L.init(K);
+  knn_walk(Q, base, lane, valid, q, L);
+  if (!valid) return;
+  const size_t row = (size_t)Q.order[i] * (size_t)K;
+#pragma unroll
+  for (int k = 0; k < KCAP; ++k) {
+    const int col = k - (KCAP - K);
+    if (col < 0) continue;
+    const uint32_t id = (uint32_t)L.e[k];
+    dists[row + col] = __uint_as_float((uint32_t)(L.e[k] >> 32));
+    idx[row + col] = id == KNN_NO_INDEX ? -1ll : (long long)id;
+  }
 }
 
 size_t knn_workspace_bytes(int P) {
@@ -342,7 +438,8 @@ size_t knn_workspace_bytes(int P) {
   return bytes;
 }
 
-int launch_knn_mean_dist(int P, const float* points, float* out, void* ws, hipStream_t stream) {
+// bbox, Morton codes, sort, SoA boxes and the AABB hierarchy of `points`, in `ws`: what both queries walk
+static KnnQuery knn_build_tree(int P, const float* points, void* ws, hipStream_t stream) {
   KnnWork w = KnnWork::carve(ws, P, nullptr);
   const int blocks = div_up(P, 256);
   const int nparts = min(blocks, KNN_BBOX_BLOCKS);
@@ -375,8 +472,29 @@ int launch_knn_mean_dist(int P, const float* points, float* out, void* ws, hipSt
   Q.bpts = w.bpts;
   for (int l = 0; l < 3; ++l) Q.lo[l] = w.lo[l], Q.hi[l] = w.hi[l], Q.n[l] = w.n[l];
   Q.order = w.vals[r];
+  Q.out = nullptr;
+  return Q;
+}
+
+int launch_knn_mean_dist(int P, const float* points, float* out, void* ws, hipStream_t stream) {
+  KnnQuery Q = knn_build_tree(P, points, ws, stream);
   Q.out = out;
   hipLaunchKernelGGL(k_knn_query, dim3((unsigned)div_up(div_up(P, 64), 4)), dim3(256), 0, stream, Q);
+  return 0;
+}
+
+int launch_knn_points(int P, int K, const float* points, float* dists, long long* idx, void* ws, hipStream_t stream) {
+  const KnnQuery Q = knn_build_tree(P, points, ws, stream);
+  const dim3 grid((unsigned)div_up(div_up(P, 64), 4)), block(256);
+  // the next list capacity up: the kernel writes only K columns
+  if (K <= 4)
+    hipLaunchKernelGGL(k_knn_points<4>, grid, block, 0, stream, Q, K, dists, idx);
+  else if (K <= 8)
+    hipLaunchKernelGGL(k_knn_points<8>, grid, block, 0, stream, Q, K, dists, idx);
+  else if (K <= 16)
+    hipLaunchKernelGGL(k_knn_points<16>, grid, block, 0, stream, Q, K, dists, idx);
+  else
+    hipLaunchKernelGGL(k_knn_points<32>, grid, block, 0, stream, Q, K, dists, idx);
   return 0;
 }
 

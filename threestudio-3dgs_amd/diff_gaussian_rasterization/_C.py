@@ -67,6 +67,8 @@ SIGNATURES = {
     "gsr_sort_rank_mode": (_i, []),
     "gsr_knn_workspace_bytes": (_sz, [_i]),
     "gsr_knn_mean_dist": (_i, [_i, _vp, _vp, _vp, _sz, _vp]),
+    "gsr_knn_points_workspace_bytes": (_sz, [_i, _i]),
+    "gsr_knn_points": (_i, [_i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gsr_set_geom_bytes": (_sz, [_i, _i]),
     "gsr_set_binning_bytes": (_sz, [_i, _i, ctypes.POINTER(_i), _i, _i]),
     "gsr_set_image_bytes": (_sz, [_i, _i, _i]),
@@ -157,7 +159,7 @@ def host_trace_read(reset: bool = True) -> dict:
     return out
 
 
-ABI_VERSION = 5  # include/gsr.h GSR_ABI_VERSION this binding is written against
+ABI_VERSION = 6  # include/gsr.h GSR_ABI_VERSION this binding is written against
 
 
 def load_library(path: str | None = None):
