@@ -54,18 +54,21 @@ extern "C" {
 const char* gsr_version(void);
 /*
  * ABI revision of this header (GSR_ABI_VERSION), for callers binding the library at run time.
- *   2  gsr_set_backward* `accumulate` CONTINUES every per-Gaussian sum from the stored value in view order
+ *   2  gsr_set_backward `accumulate` CONTINUES every per-Gaussian sum from the stored value in view order
  *      (round 1's revision 1 added the new sums to the stored values); with accumulate in the scale / rotation
  *      path dL_dcov3D is required (the running dL/dcov3D carry), otherwise GSR_EINVAL.
  *   3  gsr_shade_views_forward / gsr_shade_views_backward (per-view light colours and shading modes);
- *      gsr_set_backward_chunks / gsr_grad_chunk_range (per-Gaussian sums in ranges, events for overlap).
- *   4  gsr_set_image_bytes_ex (image buffers sized for the forward's split decision, which the buffer records);
+ *      gsr_grad_chunk_range (per-Gaussian sums in ranges, events for overlap).
+ *   4  gsr_set_image_bytes by instance counts (sized for the forward's split decision, which the buffer records);
  *      gsr_profile_kernel (the blend kernels the phases ran).
  *   5  gsr_sort_work_bytes / gsr_sort_pairs / gsr_sort_rank_mode (the library's sort, for tests);
- *      gsr_set_preprocess_ex (the two-colour render's second colours written into the records).
+ *      gsr_set_preprocess with colors2 (the two-colour render's second colours written into the records).
  *   6  gsr_knn_points_workspace_bytes / gsr_knn_points (the K nearest neighbours with indices).
+ *   7  the view-set calls take argument structs (gsr_set_scene / _state / _outputs / _grads): one gsr_set_render and
+ *      one gsr_set_backward, their variants selected by fields; the _ex, _composite, _colors, _two_colors and
+ *      _chunks entry points of revisions 2-5 are gone.
  */
-#define GSR_ABI_VERSION 6
+#define GSR_ABI_VERSION 7
 int gsr_abi_version(void);
 /* Message of the last failing call on this thread ("" if none). */
 const char* gsr_last_error(void);
@@ -142,45 +145,142 @@ int gsr_backward(int P, int degree, int M, int K, int width, int height, const f
  * color (V,3,H,W), depth / alpha (V,1,H,W), radii (V,P) int32, dL_dmeans2D (V,P,3).
  * Shared-parameter gradients (means3D, opacity, SH, scales, rotations, cov3D, colors) are summed
  * over the V views inside the per-Gaussian kernel.
+ * The arguments travel in four structs; the calls read them and keep no pointer to them.
  */
 #define GSR_SET_MAX 64
+#define GSR_GRAD_CHUNKS_MAX 16
+#define GSR_GRAD_CHUNK_ALIGN 4096
+
+/* What gsr_set_preprocess, gsr_set_render and gsr_set_backward all take: the Gaussians (shapes and the
+ * exactly-one-of rules as for gsr_forward_preprocess; M is ignored without shs) and the V cameras. */
+typedef struct gsr_set_scene {
+  int V, P, degree, M, width, height, prefiltered;
+  float scale_modifier;
+  const float *means3D, *scales, *rotations, *opacities, *shs, *colors_precomp, *cov3D_precomp;
+  /* host arrays of V device pointers: 4x4 matrices, camera positions (3,), background colours (3,) */
+  const float *const *viewmatrices, *const *projmatrices, *const *campos, *const *bgs;
+  const float *tanfovx, *tanfovy; /* host arrays of V values */
+} gsr_set_scene;
+
+/* The forward state of one set.  radii (V,P) and geom are written by gsr_set_preprocess; binning and image by
+ * gsr_set_render, given num_rendered = the host array of V counts K from gsr_set_num_rendered (K = the
+ * reference's num_rendered, the tiles of every visible Gaussian's 3-sigma rectangle: the capacity the binning and
+ * backward scratch are sized by).  gsr_set_backward reads all of it and writes none, so it may be repeated.
+ * The binning buffer belongs to this one forward until its last backward: besides the sorted tile lists the
+ * forward may keep per listed instance a quadrant-mask byte in the buffer's second (free) key array, which the
+ * backward's cull reads (csrc/gsr_common.h BinningState); the caller must not reuse the buffer in between. */
+typedef struct gsr_set_state {
+  int* radii;
+  void *geom, *binning, *image;
+  const int* num_rendered;
+} gsr_set_state;
+
+/* What gsr_set_render writes, and the optional fields that select what else its one blend pass forms. */
+typedef struct gsr_set_outputs {
+  float *out_color, *out_depth, *out_alpha; /* required */
+  /*
+   * out_render (V,3,H,W) non-NULL: the renderers' epilogue fused into the blend; the outputs above are written too.
+   * With bg_images (V,H,W,3), the background network's outputs: the background renderer's composite (replaces
+   * gsr_set_render + gsr_composite_forward for renderer/diff_gaussian_rasterizer_background.py:129-132,139),
+   * out_render = clamp(color + (1 - alpha) bg, 0, 1), bit-identical to the torch expression on the stored outputs.
+   * bg_images NULL: the clamp alone, out_render = clamp(color, 0, 1), the renderers' `rendered_image.clamp(0, 1)`
+   * (renderer/diff_gaussian_rasterizer.py:141, renderer/diff_sugar_rasterizer_normal.py:212), bit-identical too.
+   * bg_images needs out_render.
+   */
+  const float* bg_images;
+  float* out_render;
+  /*
+   * Both non-NULL: two rasterizer calls that differ only in their colours, sharing one geometry (the SuGaR normal
+   * renderer, renderer/diff_sugar_rasterizer_normal.py:157-191: the same Gaussians, camera and settings rendered
+   * with the SH / override colours, then with colors_precomp = the face normals and a zero means2D).  The second
+   * call's preprocess, sorts, binning and blend weights are the first's, so the forward blends both colour sets in
+   * one pass: out_color2 (V,3,H,W) = the blend of colors2 (P,3) with the same weights and background, the second
+   * call's colour output (its radii / depth / alpha equal the first call's).  Both or neither.
+   * A set preprocessed with colors2 (gsr_set_preprocess) holds each Gaussian's second colour in its records and
+   * remembers the pointer; the two-colour blends given that pointer read the records, given another they gather
+   * from the array.  The pointer is the only key: the CONTENTS of colors2 must not change between
+   * gsr_set_preprocess and the set's last backward.
+   */
+  const float* colors2;
+  float* out_color2;
+} gsr_set_outputs;
+
+/* What gsr_set_backward reads and writes besides the scene and the forward state. */
+typedef struct gsr_set_grads {
+  /* dL/d(out_color) (V,3,H,W), or dL/d(out_render) when `color` is given; depth / alpha (V,1,H,W) may be NULL (zero) */
+  const float *dL_dcolor, *dL_ddepth, *dL_dalpha;
+  /*
+   * color = the forward's out_color: the backward of a forward with out_render.  The blend's per-pixel prologue
+   * masks dL/drender by the clamp (recomputed from color) and, with bg_images, adds dL/dalpha += -sum_c g_c bg_c
+   * and forms dL_dbg (V,H,W,3) = g (1 - alpha) (NULL: not formed) — replaces gsr_composite_backward +
+   * gsr_set_backward.  bg_images needs color; dL_dbg needs bg_images.
+   */
+  const float *color, *bg_images;
+  float* dL_dbg;
+  /*
+   * The second call's backward of a two-colour forward on its own, on the shared forward state: colours =
+   * colors_override (P,3), dL_dcolor = dL/d(out_color2), dL_dcolors = the gradient of colors_override, dL_dmeans2D
+   * that call's screen-space gradient (the reference discards it: pass scratch).  That call has no SH, depth or alpha
+   * gradient: scene->shs, dL_ddepth, dL_dalpha and dL_dsh must be NULL.  With accumulate the parameter gradients
+   * continue the first call's.
+   */
+  const float* colors_override;
+  /*
+   * All three non-NULL: both calls' backward in one pass (replaces a plain or composite call followed by a
+   * colors_override call): the blend is replayed once, forming both calls' dL/dalpha.  dL_dcolor2 = dL/d(out_color2),
+   * dL_dcolors2 (P,3) = the gradient of colors2; dL_dmeans2D receives the first call's screen-space gradient only
+   * (the second call's means2D is the reference's fresh zero tensor); the parameter gradients hold both calls'
+   * (equal to the two-call sequence up to fp32 summation order).  All or none, and not with colors_override.
+   * colors2 as in gsr_set_outputs.  Scratch: gsr_set_backward_bytes with two_colors != 0 (64-byte gradient rows).
+   */
+  const float *colors2, *dL_dcolor2;
+  float* dL_dcolors2;
+  /*
+   * Outputs, shapes and NULL rules as for gsr_backward, summed over the set's views; dL_dmeans2D (V,P,3) is per view
+   * and always overwritten.  accumulate = 0: overwritten; != 0: every per-Gaussian sum resumes from the stored value
+   * in view order (a later set of the same batch, or the colors_override call after the first).  With accumulate in
+   * the scale / rotation path dL_dcov3D is required: it carries the running dL/dcov3D that the scale and rotation
+   * gradients are recomputed from.
+   */
+  float *dL_dmeans2D, *dL_dcolors, *dL_dopacity, *dL_dmeans3D, *dL_dcov3D, *dL_dsh, *dL_dscales, *dL_drotations;
+  int accumulate;
+  /* Scratch for the gradient rows and per-(view, Gaussian) records.  gsr_set_backward_bytes holds all V views; less
+   * is accepted (>= what the largest single view needs) and the views are then walked in groups that fit.  Any
+   * grouping gives bitwise the same gradients. */
+  void* work;
+  size_t work_bytes;
+  /*
+   * Overlap of the per-Gaussian sums with their reduction across ranks.  n_chunks = 0: the final
+   * per-Gaussian gradients are formed in one pass after the backward blend.  1..GSR_GRAD_CHUNKS_MAX: in that many
+   * Gaussian ranges, recording chunk_events[c] (hipEvent_t; the array required, an entry may be NULL) on the stream
+   * after range c, so that the caller can start reducing range c (e.g. an RCCL all-reduce on another stream waiting
+   * on the event) while the later ranges are computed.  Range c = [c S, min(P, (c + 1) S)) with
+   * S = GSR_GRAD_CHUNK_ALIGN x ceil(ceil(P / n_chunks) / ALIGN) (gsr_grad_chunk_range); ranges may be empty.
+   * Results are bitwise those of the unchunked call.
+   */
+  int n_chunks;
+  void* const* chunk_events;
+} gsr_set_grads;
+
 size_t gsr_set_geom_bytes(int V, int P);
 size_t gsr_set_binning_bytes(int V, int P, const int* num_rendered, int width, int height);
-size_t gsr_set_image_bytes(int V, int width, int height);
-/* The image bytes of exactly this forward (gsr_set_image_bytes is the upper bound): the split backward's
- * checkpoints only when the forward writes them (a launch of <= 4096 tiles on the quadrant waves, one colour
- * set: 335 MB for one 1024^2 view, held until the backward).  two_colors != 0: gsr_set_render_two_colors.
- * The forward records its decision in the buffer; the backward follows it whatever the environment says then. */
-size_t gsr_set_image_bytes_ex(int V, int P, const int* num_rendered, int width, int height, int two_colors);
-/* Scratch holding the gradient rows and per-(view, Gaussian) records of all V views; gsr_set_backward
- * also accepts less (>= what the largest single view needs) and then walks the views in groups that fit. */
-size_t gsr_set_backward_bytes(int V, int P, const int* num_rendered);
-int gsr_set_preprocess(int V, int P, int degree, int M, const float* means3D, const float* scales,
-                       float scale_modifier, const float* rotations, const float* opacities, const float* shs,
-                       const float* colors_precomp, const float* cov3D_precomp,
-                       const float* const* viewmatrices, const float* const* projmatrices,
-                       const float* const* campos, const float* tanfovx, const float* tanfovy,
-                       int width, int height, int prefiltered, int* radii, void* geom, void* stream);
-/* As gsr_set_preprocess, for a set that gsr_set_render_two_colors will blend with colors2 (P, 3) as the second
- * colour set (the SuGaR renderers' second rasterizer call): the preprocess writes each Gaussian's second colour
- * into the per-(view, Gaussian) record it writes anyway (no extra traffic), so the two-colour blends read it with
- * the record instead of gathering it from colors2 apart.  A two-colour call given another colors2 array reads
- * that array (the set remembers which pointer it embedded).  colors2 NULL = gsr_set_preprocess. */
-int gsr_set_preprocess_ex(int V, int P, int degree, int M, const float* means3D, const float* scales,
-                          float scale_modifier, const float* rotations, const float* opacities, const float* shs,
-                          const float* colors_precomp, const float* cov3D_precomp,
-                          const float* const* viewmatrices, const float* const* projmatrices,
-                          const float* const* campos, const float* tanfovx, const float* tanfovy,
-                          int width, int height, int prefiltered, int* radii, void* geom, const float* colors2,
-                          void* stream);
-/* One D2H read of every view's K (and visible count, may be NULL); synchronises `stream`.
- * K = the reference's num_rendered (tiles of every visible Gaussian's 3-sigma rectangle): the
- * capacity the binning and backward scratch are sized by. */
-int gsr_set_num_rendered(int V, const void* geom, int P, int* num_rendered, int* num_visible, void* stream);
-/* As gsr_set_num_rendered, plus num_listed[v] (may be NULL): the instances the tile lists actually
- * hold after the exact ellipse-vs-tile culling (<= K).  Diagnostic / roofline use. */
-int gsr_set_num_rendered_ex(int V, const void* geom, int P, int* num_rendered, int* num_visible, int* num_listed,
-                            void* stream);
+/* The image bytes of the forward with these counts: with the split backward's checkpoints only when the forward
+ * writes them (a launch of <= 4096 tiles on the quadrant waves, one colour set: 335 MB for one 1024^2 view, held
+ * until the backward); two_colors != 0: a render with colors2.  The forward records its decision in the buffer;
+ * the backward follows it whatever the environment says then.  num_rendered NULL: the upper bound over all counts. */
+size_t gsr_set_image_bytes(int V, int P, const int* num_rendered, int width, int height, int two_colors);
+/* gsr_set_grads.work for all V views in one group (two_colors != 0: the one-pass two-colour backward).  0 for a bad
+ * V or a NULL or negative count. */
+size_t gsr_set_backward_bytes(int V, int P, const int* num_rendered, int two_colors);
+/* Phase 1 of the set: writes state->radii and state->geom.  colors2 (P,3) non-NULL: the set will be blended with it
+ * as the second colour set; the preprocess writes each Gaussian's second colour into the per-(view, Gaussian) record
+ * it writes anyway (no extra traffic), see gsr_set_outputs.colors2. */
+int gsr_set_preprocess(const gsr_set_scene* scene, const gsr_set_state* state, const float* colors2, void* stream);
+/* One D2H read of every view's K, visible count (may be NULL) and num_listed (may be NULL): the instances the tile
+ * lists actually hold after the exact ellipse-vs-tile culling (<= K), for diagnostics and rooflines.
+ * Synchronises `stream`. */
+int gsr_set_num_rendered(int V, const void* geom, int P, int* num_rendered, int* num_visible, int* num_listed,
+                         void* stream);
 /* Diagnostic copy (device to device, on `stream`) of the preprocess state of every (view, Gaussian):
  * out_rec (V, P, 16) 32-bit words = (pixel x, pixel y, conic a, conic b | conic c, opacity, view depth, 0 |
  * r, g, b, 0 | tile rect xmin | ymin << 16, xmax | ymax << 16, 0, SH clamp flags), written only for
@@ -188,123 +288,11 @@ int gsr_set_num_rendered_ex(int V, const void* geom, int P, int* num_rendered, i
  * alpha >= 1/255 ellipse reaches).  Either may be NULL.  Parity tests compare these with the oracle's
  * per-Gaussian preprocess values (the reference's geomBuffer has no public layout). */
 int gsr_set_gauss_state(int V, const void* geom, int P, void* out_rec, void* out_tiles, void* stream);
-/* The binning buffer belongs to this one forward until its last backward: besides the sorted tile lists the
- * forward may keep per listed instance a quadrant-mask byte in the buffer's second (free) key array, which the
- * backward's cull reads (csrc/gsr_common.h BinningState); the caller must not reuse the buffer in between. */
-int gsr_set_render(int V, int P, const int* num_rendered, int width, int height, const float* const* bgs,
-                   void* geom, void* binning, void* image, float* out_color, float* out_depth,
-                   float* out_alpha, void* stream);
-/* Gradient outputs are overwritten (accumulate = 0) or continued (accumulate != 0: every per-Gaussian
- * sum resumes from the stored value in view order), summed over the set's views; dL_dmeans2D is per view
- * and always overwritten.  The views are processed in groups that fit work_bytes
- * (gsr_set_backward_bytes = all in one group); any grouping gives bitwise the same gradients.  With
- * accumulate in the scale / rotation path, dL_dcov3D is required: it carries the running dL/dcov3D
- * that the scale and rotation gradients are recomputed from.  Reads forward state only. */
-int gsr_set_backward(int V, int P, int degree, int M, const int* num_rendered, int width, int height,
-                     const float* const* bgs, const float* means3D, const float* scales, float scale_modifier,
-                     const float* rotations, const float* shs, const float* cov3D_precomp,
-                     const float* const* viewmatrices, const float* const* projmatrices,
-                     const float* const* campos, const float* tanfovx, const float* tanfovy, const int* radii,
-                     const void* geom, const void* binning, const void* image, const float* dL_dcolor,
-                     const float* dL_ddepth, const float* dL_dalpha, float* dL_dmeans2D, float* dL_dcolors,
-                     float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
-                     float* dL_dscales, float* dL_drotations, int accumulate, void* work, size_t work_bytes,
+int gsr_set_render(const gsr_set_scene* scene, const gsr_set_state* state, const gsr_set_outputs* outputs,
+                   void* stream);
+int gsr_set_backward(const gsr_set_scene* scene, const gsr_set_state* state, const gsr_set_grads* grads,
                      void* stream);
-/*
- * Overlap of the per-Gaussian sums with their reduction across ranks.  A backward's final
- * per-Gaussian gradients are formed in one pass after the backward blend; gsr_set_backward_chunks asks the
- * NEXT gsr_set_backward* call made on this thread to form them in n_chunks Gaussian ranges instead, recording
- * events[c] (hipEvent_t, may be NULL) on the stream after range c, so that the caller can start reducing range
- * c (e.g. an RCCL all-reduce on another stream waiting on the event) while the later ranges are computed.
- * Range c = [c S, min(P, (c + 1) S)) with S = GSR_GRAD_CHUNK_ALIGN x ceil(ceil(P / n_chunks) / ALIGN)
- * (gsr_grad_chunk_range); ranges may be empty.  Results are bitwise those of the unchunked call.  The request
- * applies to one call only (n_chunks = 0 cancels it).
- */
-#define GSR_GRAD_CHUNKS_MAX 16
-#define GSR_GRAD_CHUNK_ALIGN 4096
-int gsr_set_backward_chunks(int n_chunks, void* const* events);
 int gsr_grad_chunk_range(int P, int n_chunks, int chunk, int* g0, int* g1);
-
-/*
- * Two rasterizer calls that differ only in their colours, sharing one geometry (the SuGaR normal renderer,
- * renderer/diff_sugar_rasterizer_normal.py:157-191: the same Gaussians, camera and settings rendered with
- * the SH / override colours, then with colors_precomp = the face normals and a zero means2D).  The second
- * call's preprocess, sorts and binning are the first's; its blend weights too, so the forward blends both
- * colour sets in one pass:
- *   gsr_set_render_two_colors  as gsr_set_render (bg_images / out_render: the fused composite, both NULL
- *                              for none; out_render alone: the clamp alone, as gsr_set_render_composite)
- *                              plus out_color2 (V, 3, H, W) = the blend of colors2 (P, 3) with
- *                              the same weights and background: the second call's colour output (its
- *                              radii / depth / alpha equal the first call's).
- *   gsr_set_backward_colors    the second call's backward on the shared forward state: colours = colors2,
- *                              dL_dcolor = dL/d(out_color2), no depth / alpha gradient, no SH; dL_dmeans2D
- *                              receives the second call's screen-space gradient (the reference discards it:
- *                              pass scratch), dL_dcolors the gradient of colors2.  With accumulate the
- *                              parameter gradients continue the first call's (gsr_set_backward with
- *                              dL_dcov3D as the running dL/dcov3D carry).
- *   gsr_set_backward_two_colors  both calls' backward in one pass (replaces gsr_set_backward[_composite]
- *                              followed by gsr_set_backward_colors): the blend is replayed once, forming
- *                              both calls' dL/dalpha; arguments as gsr_set_backward_composite (bg_images
- *                              and color both NULL: no composite; color alone: the clamp alone) plus colors2,
- *                              dL_dcolor2 = dL/d(out_color2)
- *                              and dL_dcolors2 (P, 3) = the gradient of colors2.  dL_dmeans2D receives the
- *                              first call's screen-space gradient only (the second call's means2D is the
- *                              reference's fresh zero tensor); the parameter gradients hold both calls'
- *                              (equal to the two-call sequence up to fp32 summation order).  Scratch:
- *                              gsr_set_backward_two_colors_bytes (64-byte gradient rows).
- */
-int gsr_set_render_two_colors(int V, int P, const int* num_rendered, int width, int height, const float* const* bgs,
-                              void* geom, void* binning, void* image, float* out_color, float* out_depth,
-                              float* out_alpha, const float* bg_images, float* out_render, const float* colors2,
-                              float* out_color2, void* stream);
-int gsr_set_backward_colors(int V, int P, const int* num_rendered, int width, int height, const float* const* bgs,
-                            const float* means3D, const float* scales, float scale_modifier, const float* rotations,
-                            const float* cov3D_precomp, const float* const* viewmatrices,
-                            const float* const* projmatrices, const float* const* campos, const float* tanfovx,
-                            const float* tanfovy, const int* radii, const void* geom, const void* binning,
-                            const void* image, const float* colors, const float* dL_dcolor, float* dL_dmeans2D,
-                            float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D,
-                            float* dL_dscales, float* dL_drotations, int accumulate, void* work, size_t work_bytes,
-                            void* stream);
-size_t gsr_set_backward_two_colors_bytes(int V, int P, const int* num_rendered);
-int gsr_set_backward_two_colors(int V, int P, int degree, int M, const int* num_rendered, int width, int height,
-                                const float* const* bgs, const float* means3D, const float* scales,
-                                float scale_modifier, const float* rotations, const float* shs,
-                                const float* cov3D_precomp, const float* const* viewmatrices,
-                                const float* const* projmatrices, const float* const* campos, const float* tanfovx,
-                                const float* tanfovy, const int* radii, const void* geom, const void* binning,
-                                const void* image, const float* bg_images, const float* color,
-                                const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
-                                float* dL_dbg, const float* colors2, const float* dL_dcolor2, float* dL_dmeans2D,
-                                float* dL_dcolors, float* dL_dcolors2, float* dL_dopacity, float* dL_dmeans3D,
-                                float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
-                                int accumulate, void* work, size_t work_bytes, void* stream);
-/*
- * The background renderer's composite fused into the blends (replaces gsr_set_render + gsr_composite_forward
- * and gsr_composite_backward + gsr_set_backward for renderer/diff_gaussian_rasterizer_background.py:129-132,139):
- * bg_images (V, H, W, 3) are the background network's outputs; out_render (V, 3, H, W) =
- * clamp(color + (1 - alpha) bg, 0, 1), bit-identical to the torch expression on the stored outputs; the
- * colour / depth / alpha outputs are written as by gsr_set_render.  The backward takes dL/drender in
- * place of dL/dcolor, the forward's colour output, and forms dL/dbg (NULL: not formed) in the blend's
- * per-pixel prologue (clamp mask, dL/dalpha += -sum_c g_c bg_c, dL/dbg = g (1 - alpha)).
- * bg_images NULL: the clamp alone — out_render = clamp(color, 0, 1), the renderers' `rendered_image.clamp(0, 1)`
- * (renderer/diff_gaussian_rasterizer.py:141, renderer/diff_sugar_rasterizer_normal.py:212) bit-identical to the
- * torch expression; the backward masks dL/drender by the forward's colour (dL_dbg must be NULL).
- */
-int gsr_set_render_composite(int V, int P, const int* num_rendered, int width, int height, const float* const* bgs,
-                             void* geom, void* binning, void* image, float* out_color, float* out_depth,
-                             float* out_alpha, const float* bg_images, float* out_render, void* stream);
-int gsr_set_backward_composite(int V, int P, int degree, int M, const int* num_rendered, int width, int height,
-                               const float* const* bgs, const float* means3D, const float* scales,
-                               float scale_modifier, const float* rotations, const float* shs,
-                               const float* cov3D_precomp, const float* const* viewmatrices,
-                               const float* const* projmatrices, const float* const* campos, const float* tanfovx,
-                               const float* tanfovy, const int* radii, const void* geom, const void* binning,
-                               const void* image, const float* bg_images, const float* color,
-                               const float* dL_drender, const float* dL_ddepth, const float* dL_dalpha,
-                               float* dL_dbg, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
-                               float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
-                               float* dL_drotations, int accumulate, void* work, size_t work_bytes, void* stream);
 
 /*
  * Optional phase timing with HIP events recorded on the launch stream around each phase's kernels.

@@ -148,7 +148,7 @@ def _worker(rank, world, port, tmp, B, overlap=False):
 @pytest.mark.parametrize("B,overlap", [(5, False), (4, False), (5, True)])
 def test_sharded_hip_path_world2(B, overlap, tmp_path):
     """overlap: ChunkedGradReduce — the per-Gaussian backward in Gaussian ranges with an event after each,
-    each range's rows all-reduced on a side stream while the next is formed (gsr_set_backward_chunks)."""
+    each range's rows all-reduced on a side stream while the next is formed (gsr_set_grads.n_chunks)."""
     import torch.multiprocessing as mp
 
     _step((0, 1), B, str(tmp_path), "single")
@@ -260,7 +260,7 @@ def test_chunked_reduce_reads_finished_gradients(bwd):
 
 @pytest.mark.parametrize("n_chunks,P", [(4, 20_000), (3, 4096 * 5 + 17), (16, 9000)])
 def test_chunked_gauss_backward_bitwise(n_chunks, P):
-    """gsr_set_backward_chunks: the per-Gaussian backward in Gaussian ranges (with events) gives bitwise the
+    """gsr_set_grads.n_chunks: the per-Gaussian backward in Gaussian ranges (with events) gives bitwise the
     gradients of the one-pass backward, also with the background composite and several view sets."""
     from diff_gaussian_rasterization import GaussianRasterizationSettings
     from diff_gaussian_rasterization.batched import rasterize_views

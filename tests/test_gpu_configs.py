@@ -254,7 +254,7 @@ def test_backward_view_groups_bitwise(monkeypatch):
     import ctypes
 
     Ks = (ctypes.c_int * 6)(*one["K"])
-    need = int(lib.gsr_set_backward_bytes(6, 20_000, Ks))
+    need = int(lib.gsr_set_backward_bytes(6, 20_000, Ks, 0))
     largest = max(int(lib.gsr_backward_bytes(20_000, k)) for k in one["K"])
     assert largest * 3 <= need, "the split must produce at least 3 groups"
     split = _batched_grads(scene, cams, ups, monkeypatch, budget=1)  # work = one view's bytes: 6 groups
@@ -527,7 +527,7 @@ def test_second_colors_match_separate_call(bwd, monkeypatch):
     equal; parameter gradients (summed over both calls) within 1e-5 relative when the backward runs the two
     calls one after the other (two_color_backward="separate"), and then the first call's means2D gradient is
     bitwise the one-colour backward's.  The one-pass two-colour backward
-    (gsr_set_backward_two_colors) adds both calls' dL/dalpha per pixel before the moments and the chain
+    (gsr_set_backward with colors2) adds both calls' dL/dalpha per pixel before the moments and the chain
     rule, an fp32 reassociation of the two-call sum (measured up to 1.6e-4 max(1, |g|) apart from the
     two-call sequence where the calls' gradients cancel): it is held to the fp64 oracle's two summed
     backward passes with the gradient bar of every parity test (check_grads); its sums come from hit lists
@@ -610,10 +610,10 @@ def test_second_colors_match_separate_call(bwd, monkeypatch):
 
 
 def test_two_color_backward_groups_and_sets_bitwise(monkeypatch):
-    """The one-pass two-colour backward (gsr_set_backward_two_colors) walked in view groups that fit a small
+    """The one-pass two-colour backward (gsr_set_backward with colors2) walked in view groups that fit a small
     work buffer, and over several view sets (accumulate: dL/dcolors2 and the running dL/dcov3D continue in
     view order): bitwise the gradients of one group / one set.  And the second colours read from the records the
-    preprocess embedded them in (gsr_set_preprocess_ex, the default) against gathered from colors2 apart: the same
+    preprocess embedded them in (gsr_set_preprocess with colors2, the default) against gathered from colors2 apart: the same
     images and gradients, bit for bit."""
     import torch
 
@@ -661,7 +661,7 @@ def test_two_color_backward_groups_and_sets_bitwise(monkeypatch):
 def test_two_color_backward_with_fused_composite():
     """rasterize_views(background=..., colors2=...): the background renderer's fused composite on the first
     colour set and a second colour set in the same forward and the same one-pass backward
-    (gsr_set_render_two_colors / gsr_set_backward_two_colors with bg_images): the parameter, background and
+    (gsr_set_render / gsr_set_backward with colors2 and bg_images): the parameter, background and
     colors2 gradients against the fp64 oracle's two backward passes with the composite's upstream gradients
     (renderer/diff_gaussian_rasterizer_background.py:129-132,139 restated in _composite_upstream)."""
     import torch

@@ -113,30 +113,26 @@ static int effective_degree(int degree, int M) {
 static int tile_sort_result(int W, int H) { return digit_plan(tile_key_bits(W, H)).passes & 1; }
 static int depth_sort_result() { return digit_plan(32).passes & 1; }
 
-static GaussBackwardArgs shared_args(int P, int degree, int M, const float* means3D, const float* scales,
-                                     float scale_modifier, const float* rotations, const float* shs,
-                                     const float* cov3D_precomp, float* dL_dcolors, float* dL_dopacity,
-                                     float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
-                                     float* dL_drotations) {
+static GaussBackwardArgs shared_args(const gsr_set_scene& sc, const gsr_set_grads& gr) {
   GaussBackwardArgs a;
-  a.P = P;
+  a.P = sc.P;
   a.g0 = 0;
-  a.g1 = P;
-  a.deg = effective_degree(degree, M);
-  a.M = shs ? M : 0;
-  a.means3D = means3D;
-  a.scales = scales;
-  a.rotations = rotations;
-  a.shs = shs;
-  a.cov3D_precomp = cov3D_precomp;
-  a.scale_modifier = scale_modifier;
-  a.dL_dcolors = dL_dcolors;
-  a.dL_dopacity = dL_dopacity;
-  a.dL_dmeans3D = dL_dmeans3D;
-  a.dL_dcov3D = dL_dcov3D;
-  a.dL_dsh = shs ? dL_dsh : nullptr;
-  a.dL_dscales = cov3D_precomp ? nullptr : dL_dscales;
-  a.dL_drotations = cov3D_precomp ? nullptr : dL_drotations;
+  a.g1 = sc.P;
+  a.M = sc.shs ? sc.M : 0;
+  a.deg = effective_degree(sc.degree, a.M);
+  a.means3D = sc.means3D;
+  a.scales = sc.scales;
+  a.rotations = sc.rotations;
+  a.shs = sc.shs;
+  a.cov3D_precomp = sc.cov3D_precomp;
+  a.scale_modifier = sc.scale_modifier;
+  a.dL_dcolors = gr.dL_dcolors;
+  a.dL_dopacity = gr.dL_dopacity;
+  a.dL_dmeans3D = gr.dL_dmeans3D;
+  a.dL_dcov3D = gr.dL_dcov3D;
+  a.dL_dsh = sc.shs ? gr.dL_dsh : nullptr;
+  a.dL_dscales = sc.cov3D_precomp ? nullptr : gr.dL_dscales;
+  a.dL_drotations = sc.cov3D_precomp ? nullptr : gr.dL_drotations;
   return a;
 }
 
@@ -156,19 +152,18 @@ static int inst_segments(int V, const int* K, SegInfo& seg, long long* total) {
   return GSR_OK;
 }
 
-static int set_cams(int V, const float* const* viewmatrices, const float* const* projmatrices,
-                    const float* const* campos, const float* tanfovx, const float* tanfovy, SetCams& cams) {
-  if (viewmatrices == nullptr || projmatrices == nullptr || campos == nullptr || tanfovx == nullptr ||
-      tanfovy == nullptr)
+static int set_cams(const gsr_set_scene& sc, SetCams& cams) {
+  if (sc.viewmatrices == nullptr || sc.projmatrices == nullptr || sc.campos == nullptr || sc.tanfovx == nullptr ||
+      sc.tanfovy == nullptr)
     return fail(GSR_EINVAL, "%s", "null camera array");
-  for (int v = 0; v < V; ++v) {
-    if (viewmatrices[v] == nullptr || projmatrices[v] == nullptr || campos[v] == nullptr)
+  for (int v = 0; v < sc.V; ++v) {
+    if (sc.viewmatrices[v] == nullptr || sc.projmatrices[v] == nullptr || sc.campos[v] == nullptr)
       return fail(GSR_EINVAL, "%s", "null camera pointer");
-    cams.c[v].view = viewmatrices[v];
-    cams.c[v].proj = projmatrices[v];
-    cams.c[v].campos = campos[v];
-    cams.c[v].tanx = tanfovx[v];
-    cams.c[v].tany = tanfovy[v];
+    cams.c[v].view = sc.viewmatrices[v];
+    cams.c[v].proj = sc.projmatrices[v];
+    cams.c[v].campos = sc.campos[v];
+    cams.c[v].tanx = sc.tanfovx[v];
+    cams.c[v].tany = sc.tanfovy[v];
   }
   return GSR_OK;
 }
@@ -198,90 +193,79 @@ size_t gsr_set_geom_bytes(int V, int P) {
   GeomState::carve(nullptr, V, P, &b);
   return b;
 }
+// instance total of a set for the sizers: false for a bad V or a NULL / negative / overflowing count
+static bool set_total(int V, const int* K, SegInfo& seg, long long* total) {
+  return V >= 1 && V <= GSR_SET_MAX && K != nullptr && inst_segments(V, K, seg, total) == GSR_OK;
+}
 size_t gsr_set_binning_bytes(int V, int P, const int* K, int width, int height) {
   SegInfo seg;
   long long total = 0;
-  if (V < 1 || V > GSR_SET_MAX || K == nullptr || inst_segments(V, K, seg, &total) != GSR_OK) return 0;
+  if (!set_total(V, K, seg, &total)) return 0;
   size_t b = 0;
   BinningState::carve(nullptr, V, total, seg.blk[V], !set_tile_pack(P, width, height).packed, &b);
   return b;
 }
-size_t gsr_set_image_bytes(int V, int width, int height) {
-  size_t b = 0;
-  ImageState::carve(nullptr, V, width, height, &b);
-  return b;
-}
-size_t gsr_set_image_bytes_ex(int V, int P, const int* K, int width, int height, int two_colors) {
+size_t gsr_set_image_bytes(int V, int P, const int* K, int width, int height, int two_colors) {
   SegInfo seg;
   long long total = 0;
-  if (V < 1 || V > GSR_SET_MAX || K == nullptr || inst_segments(V, K, seg, &total) != GSR_OK) return 0;
+  if (K != nullptr && !set_total(V, K, seg, &total)) return 0;
   size_t b = 0;
-  ImageState::carve(nullptr, V, width, height, &b, split_forward(V, P, width, height, total, two_colors != 0));
+  // (no counts: the upper bound, with the split backward's checkpoints)
+  ImageState::carve(nullptr, V, width, height, &b,
+                    K == nullptr || split_forward(V, P, width, height, total, two_colors != 0));
   return b;
 }
 // the running dL/dcov3D (P x 6) kept at the end of the work buffer across view groups
 static size_t carry_bytes(int P) { return align_up(sizeof(float) * 6 * (size_t)(P > 0 ? P : 1), 256); }
 
-size_t gsr_set_backward_bytes(int V, int P, const int* K) {
+size_t gsr_set_backward_bytes(int V, int P, const int* K, int two_colors) {
+  SegInfo seg;
   long long total = 0;
-  for (int v = 0; v < V; ++v) total += K[v];
-  return BackwardState::bytes_for(total, V, P) + carry_bytes(P);
+  if (!set_total(V, K, seg, &total)) return 0;
+  return BackwardState::bytes_for(total, V, P, two_colors != 0) + carry_bytes(P);
 }
 
-int gsr_set_preprocess(int V, int P, int degree, int M, const float* means3D, const float* scales,
-                       float scale_modifier, const float* rotations, const float* opacities, const float* shs,
-                       const float* colors_precomp, const float* cov3D_precomp, const float* const* viewmatrices,
-                       const float* const* projmatrices, const float* const* campos, const float* tanfovx,
-                       const float* tanfovy, int width, int height, int prefiltered, int* radii, void* geom,
-                       void* stream) {
-  return gsr_set_preprocess_ex(V, P, degree, M, means3D, scales, scale_modifier, rotations, opacities, shs,
-                               colors_precomp, cov3D_precomp, viewmatrices, projmatrices, campos, tanfovx, tanfovy,
-                               width, height, prefiltered, radii, geom, nullptr, stream);
-}
-
-int gsr_set_preprocess_ex(int V, int P, int degree, int M, const float* means3D, const float* scales,
-                          float scale_modifier, const float* rotations, const float* opacities, const float* shs,
-                          const float* colors_precomp, const float* cov3D_precomp, const float* const* viewmatrices,
-                          const float* const* projmatrices, const float* const* campos, const float* tanfovx,
-                          const float* tanfovy, int width, int height, int prefiltered, int* radii, void* geom,
-                          const float* colors2, void* stream) {
-  (void)prefiltered;
+int gsr_set_preprocess(const gsr_set_scene* scene, const gsr_set_state* state, const float* colors2, void* stream) {
+  if (scene == nullptr || state == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
+  const gsr_set_scene& sc = *scene;
+  const int V = sc.V, P = sc.P;
   if (check_set(V, P) != GSR_OK) return GSR_EINVAL;
-  if (width <= 0 || height <= 0) return fail(GSR_EINVAL, "%s", "image size must be positive");
-  if ((shs == nullptr) == (colors_precomp == nullptr))
+  if (sc.width <= 0 || sc.height <= 0) return fail(GSR_EINVAL, "%s", "image size must be positive");
+  if ((sc.shs == nullptr) == (sc.colors_precomp == nullptr))
     return fail(GSR_EINVAL, "%s", "Please provide exactly one of either SHs or precomputed colors!");
-  if (((scales == nullptr || rotations == nullptr) && cov3D_precomp == nullptr) ||
-      ((scales != nullptr || rotations != nullptr) && cov3D_precomp != nullptr))
+  if (((sc.scales == nullptr || sc.rotations == nullptr) && sc.cov3D_precomp == nullptr) ||
+      ((sc.scales != nullptr || sc.rotations != nullptr) && sc.cov3D_precomp != nullptr))
     return fail(GSR_EINVAL, "%s",
                 "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
-  if (geom == nullptr || (P > 0 && (means3D == nullptr || opacities == nullptr || radii == nullptr)))
+  if (state->geom == nullptr ||
+      (P > 0 && (sc.means3D == nullptr || sc.opacities == nullptr || state->radii == nullptr)))
     return fail(GSR_EINVAL, "%s", "null pointer argument");
-  if (shs != nullptr && M <= 0) return fail(GSR_EINVAL, "%s", "M must be >= 1 with SHs");
+  if (sc.shs != nullptr && sc.M <= 0) return fail(GSR_EINVAL, "%s", "M must be >= 1 with SHs");
   SetCams cams;
-  if (set_cams(V, viewmatrices, projmatrices, campos, tanfovx, tanfovy, cams) != GSR_OK) return GSR_EINVAL;
+  if (set_cams(sc, cams) != GSR_OK) return GSR_EINVAL;
   for (int v = 0; v < V; ++v) {  // IEEE float division on the host = the device's correctly rounded one
-    cams.c[v].fx = (float)width / (2.0f * cams.c[v].tanx);
-    cams.c[v].fy = (float)height / (2.0f * cams.c[v].tany);
+    cams.c[v].fx = (float)sc.width / (2.0f * cams.c[v].tanx);
+    cams.c[v].fy = (float)sc.height / (2.0f * cams.c[v].tany);
   }
   hipStream_t s = (hipStream_t)stream;
-  GeomState g = GeomState::carve(geom, V, P, nullptr);
+  GeomState g = GeomState::carve(state->geom, V, P, nullptr);
 
   PreprocessArgs a;
   a.V = V;
   a.P = P;
-  a.deg = effective_degree(degree, M);
-  a.M = M;
-  a.means3D = means3D;
-  a.scales = scales;
-  a.rotations = rotations;
-  a.opacities = opacities;
-  a.shs = shs;
-  a.colors_precomp = colors_precomp;
-  a.cov3D_precomp = cov3D_precomp;
-  a.scale_modifier = scale_modifier;
-  a.W = width;
-  a.H = height;
-  a.radii = radii;
+  a.deg = effective_degree(sc.degree, sc.M);
+  a.M = sc.M;
+  a.means3D = sc.means3D;
+  a.scales = sc.scales;
+  a.rotations = sc.rotations;
+  a.opacities = sc.opacities;
+  a.shs = sc.shs;
+  a.colors_precomp = sc.colors_precomp;
+  a.cov3D_precomp = sc.cov3D_precomp;
+  a.scale_modifier = sc.scale_modifier;
+  a.W = sc.width;
+  a.H = sc.height;
+  a.radii = state->radii;
   a.col2 = colors2;
   {
     PhaseScope ps(GSR_PHASE_PREPROCESS, s);
@@ -526,7 +510,7 @@ struct SortWork {
 size_t gsr_sort_work_bytes(int V, const int* n) {
   SegInfo seg;
   long long total = 0;
-  if (V < 1 || V > GSR_SET_MAX || n == nullptr || inst_segments(V, n, seg, &total) != GSR_OK) return 0;
+  if (!set_total(V, n, seg, &total)) return 0;
   size_t b = 0;
   SortWork::carve(nullptr, V, total, seg.blk[V], &b);
   return b;
@@ -560,8 +544,8 @@ int gsr_sort_pairs(int V, const int* n, uint32_t* keys, uint32_t* vals, int key_
 
 int gsr_sort_rank_mode(void) { return sort_rank_mode(); }
 
-int gsr_set_num_rendered_ex(int V, const void* geom, int P, int* num_rendered, int* num_visible, int* num_listed,
-                            void* stream) {
+int gsr_set_num_rendered(int V, const void* geom, int P, int* num_rendered, int* num_visible, int* num_listed,
+                         void* stream) {
   if (check_set(V, P) != GSR_OK) return GSR_EINVAL;
   if (geom == nullptr || num_rendered == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
   GeomState g = GeomState::carve((void*)geom, V, P, nullptr);
@@ -592,18 +576,23 @@ int gsr_set_gauss_state(int V, const void* geom, int P, void* out_rec, void* out
   return last_launch();
 }
 
-int gsr_set_num_rendered(int V, const void* geom, int P, int* num_rendered, int* num_visible, void* stream) {
-  return gsr_set_num_rendered_ex(V, geom, P, num_rendered, num_visible, nullptr, stream);
-}
-
-static int set_render(int V, int P, const int* K, int width, int height, const float* const* bgs, void* geom,
-                      void* binning, void* image, float* out_color, float* out_depth, float* out_alpha,
-                      const float* comp_bg, float* out_render, void* stream, const float* colors2 = nullptr,
-                      float* out_color2 = nullptr) {
+int gsr_set_render(const gsr_set_scene* scene, const gsr_set_state* state, const gsr_set_outputs* outputs,
+                   void* stream) {
+  if (scene == nullptr || state == nullptr || outputs == nullptr)
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  const gsr_set_outputs& o = *outputs;
+  const int V = scene->V, P = scene->P, width = scene->width, height = scene->height;
+  const int* K = state->num_rendered;
+  const float* const* bgs = scene->bgs;
+  void *geom = state->geom, *binning = state->binning, *image = state->image;
+  const float* colors2 = o.colors2;
   if (check_set(V, P) != GSR_OK) return GSR_EINVAL;
+  if ((colors2 == nullptr) != (o.out_color2 == nullptr)) return fail(GSR_EINVAL, "%s", "null second colour argument");
+  // (out_render without bg_images: the clamp alone)
+  if (o.bg_images != nullptr && o.out_render == nullptr) return fail(GSR_EINVAL, "%s", "composite needs out_render");
   if (width <= 0 || height <= 0) return fail(GSR_EINVAL, "%s", "bad sizes");
   if (K == nullptr || bgs == nullptr || geom == nullptr || binning == nullptr || image == nullptr ||
-      out_color == nullptr || out_depth == nullptr || out_alpha == nullptr)
+      o.out_color == nullptr || o.out_depth == nullptr || o.out_alpha == nullptr)
     return fail(GSR_EINVAL, "%s", "null pointer argument");
   SegInfo inst;
   long long total = 0;
@@ -638,13 +627,13 @@ static int set_render(int V, int P, const int* K, int width, int height, const f
   {
     PhaseScope ps(GSR_PHASE_RENDER_FWD, s);
     RenderSet rs;
-    rs.cbg = comp_bg;
-    rs.comp = out_render;
+    rs.cbg = o.bg_images;
+    rs.comp = o.out_render;
     rs.ccolor = nullptr;
     rs.dcbg = nullptr;
     rs.col2 = colors2;
     rs.col2_rec = g.drange + 130;
-    rs.out_col2 = out_color2;
+    rs.out_col2 = o.out_color2;
     rs.dpix2 = nullptr;
     rs.order = img.order;
     rs.ochunk = order_chunk(V, gx, gy, true);
@@ -669,104 +658,80 @@ static int set_render(int V, int P, const int* K, int width, int height, const f
       rs.row_start[v] = 0;
       rs.bg[v] = bgs[v];
     }
-    launch_render_forward(rs, g, tp.packed ? b.key[tres] : b.val[tres], img, out_color, out_depth, out_alpha, total,
-                          s);
+    launch_render_forward(rs, g, tp.packed ? b.key[tres] : b.val[tres], img, o.out_color, o.out_depth, o.out_alpha,
+                          total, s);
   }
   return last_launch();
 }
-
-int gsr_set_render(int V, int P, const int* K, int width, int height, const float* const* bgs, void* geom,
-                   void* binning, void* image, float* out_color, float* out_depth, float* out_alpha, void* stream) {
-  return set_render(V, P, K, width, height, bgs, geom, binning, image, out_color, out_depth, out_alpha, nullptr,
-                    nullptr, stream);
-}
-
-int gsr_set_render_composite(int V, int P, const int* K, int width, int height, const float* const* bgs, void* geom,
-                             void* binning, void* image, float* out_color, float* out_depth, float* out_alpha,
-                             const float* bg_images, float* out_render, void* stream) {
-  // (bg_images NULL: the clamp alone, out_render = clamp(color, 0, 1))
-  if (out_render == nullptr) return fail(GSR_EINVAL, "%s", "null composite argument");
-  return set_render(V, P, K, width, height, bgs, geom, binning, image, out_color, out_depth, out_alpha, bg_images,
-                    out_render, stream);
-}
-
-int gsr_set_render_two_colors(int V, int P, const int* K, int width, int height, const float* const* bgs,
-                              void* geom, void* binning, void* image, float* out_color, float* out_depth,
-                              float* out_alpha, const float* bg_images, float* out_render, const float* colors2,
-                              float* out_color2, void* stream) {
-  if (colors2 == nullptr || out_color2 == nullptr) return fail(GSR_EINVAL, "%s", "null second colour argument");
-  // (out_render without bg_images: the clamp alone)
-  if (bg_images != nullptr && out_render == nullptr) return fail(GSR_EINVAL, "%s", "composite needs out_render");
-  return set_render(V, P, K, width, height, bgs, geom, binning, image, out_color, out_depth, out_alpha, bg_images,
-                    out_render, stream, colors2, out_color2);
-}
-
-// One-shot per-thread request (gsr_set_backward_chunks) for the next backward call on this thread.
-struct GradChunks {
-  int n = 0;
-  void* events[GSR_GRAD_CHUNKS_MAX] = {};
-};
-static thread_local GradChunks g_next_chunks;
 
 static int grad_chunk_size(int P, int n) {
   const int q = (P + n - 1) / n;
   return (q + GSR_GRAD_CHUNK_ALIGN - 1) / GSR_GRAD_CHUNK_ALIGN * GSR_GRAD_CHUNK_ALIGN;
 }
 
-static int set_backward(int V, int P, int degree, int M, const int* K, int width, int height, const float* const* bgs,
-                        const float* means3D, const float* scales, float scale_modifier, const float* rotations,
-                        const float* shs, const float* cov3D_precomp, const float* const* viewmatrices,
-                        const float* const* projmatrices, const float* const* campos, const float* tanfovx,
-                        const float* tanfovy, const int* radii, const void* geom, const void* binning,
-                        const void* image, const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
-                        float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D,
-                        float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations, int accumulate,
-                        void* work, size_t work_bytes, const float* comp_bg, const float* color, float* dL_dbg,
-                        void* stream, const float* colors_override = nullptr, const float* colors2 = nullptr,
-                        const float* dL_dcolor2 = nullptr, float* dL_dcolors2 = nullptr) {
-  const GradChunks chunks = g_next_chunks;  // consumed by this call, whatever its outcome
-  g_next_chunks = GradChunks{};
+int gsr_set_backward(const gsr_set_scene* scene, const gsr_set_state* state, const gsr_set_grads* grads,
+                     void* stream) {
+  if (scene == nullptr || state == nullptr || grads == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
+  const gsr_set_scene& sc = *scene;
+  const gsr_set_grads& gr = *grads;
+  const int V = sc.V, P = sc.P, width = sc.width, height = sc.height;
+  const int* K = state->num_rendered;
+  const float* const* bgs = sc.bgs;
+  const float *colors_override = gr.colors_override, *color = gr.color, *comp_bg = gr.bg_images;
+  float *dL_dcov3D = gr.dL_dcov3D, *dL_dbg = gr.dL_dbg;
+  const float *dL_dcolor = gr.dL_dcolor, *dL_ddepth = gr.dL_ddepth, *dL_dalpha = gr.dL_dalpha;
   if (check_set(V, P) != GSR_OK) return GSR_EINVAL;
   // both rasterizer calls of the SuGaR normal renderer in one pass (64-byte rows, 17-field records)
-  const bool two = dL_dcolor2 != nullptr;
-  if (two && (colors2 == nullptr || dL_dcolors2 == nullptr || colors_override != nullptr))
+  const bool two = gr.colors2 != nullptr || gr.dL_dcolor2 != nullptr || gr.dL_dcolors2 != nullptr;
+  if (two && (gr.colors2 == nullptr || gr.dL_dcolor2 == nullptr || gr.dL_dcolors2 == nullptr ||
+              colors_override != nullptr))
     return fail(GSR_EINVAL, "%s", "two-colour backward needs colors2, dL_dcolor2 and dL_dcolors2");
+  // (the second call of a two-colour forward on its own: precomputed colours, and the reference passes it no
+  // depth / alpha gradient)
+  if (colors_override != nullptr && (sc.shs != nullptr || gr.dL_dsh != nullptr || dL_ddepth != nullptr ||
+                                     dL_dalpha != nullptr))
+    return fail(GSR_EINVAL, "%s", "colors_override excludes SHs and the depth / alpha gradients");
+  // (color without bg_images: the clamp alone; neither: no composite)
+  if (comp_bg != nullptr && color == nullptr) return fail(GSR_EINVAL, "%s", "composite needs the forward's color");
+  if (comp_bg == nullptr && dL_dbg != nullptr) return fail(GSR_EINVAL, "%s", "dL_dbg needs bg_images");
+  if (gr.n_chunks < 0 || gr.n_chunks > GSR_GRAD_CHUNKS_MAX || (gr.n_chunks > 0 && gr.chunk_events == nullptr))
+    return fail(GSR_EINVAL, "%s", "bad gradient chunk request");
   if (width <= 0 || height <= 0) return fail(GSR_EINVAL, "%s", "bad sizes");
   if (P == 0) return last_launch();
-  if (K == nullptr || bgs == nullptr || geom == nullptr || binning == nullptr || image == nullptr ||
-      work == nullptr || dL_dcolor == nullptr || dL_dmeans2D == nullptr || dL_dcolors == nullptr ||
-      dL_dopacity == nullptr || dL_dmeans3D == nullptr || radii == nullptr || means3D == nullptr)
+  if (K == nullptr || bgs == nullptr || state->geom == nullptr || state->binning == nullptr ||
+      state->image == nullptr || gr.work == nullptr || dL_dcolor == nullptr || gr.dL_dmeans2D == nullptr ||
+      gr.dL_dcolors == nullptr || gr.dL_dopacity == nullptr || gr.dL_dmeans3D == nullptr ||
+      state->radii == nullptr || sc.means3D == nullptr)
     return fail(GSR_EINVAL, "%s", "null pointer argument");
-  if (shs != nullptr && dL_dsh == nullptr) return fail(GSR_EINVAL, "%s", "dL_dsh required with SHs");
-  if (cov3D_precomp == nullptr && (scales == nullptr || rotations == nullptr || dL_dscales == nullptr ||
-                                   dL_drotations == nullptr))
+  if (sc.shs != nullptr && gr.dL_dsh == nullptr) return fail(GSR_EINVAL, "%s", "dL_dsh required with SHs");
+  if (sc.cov3D_precomp == nullptr && (sc.scales == nullptr || sc.rotations == nullptr || gr.dL_dscales == nullptr ||
+                                      gr.dL_drotations == nullptr))
     return fail(GSR_EINVAL, "%s", "scales/rotations and their gradients required");
   SetCams cams;
-  if (set_cams(V, viewmatrices, projmatrices, campos, tanfovx, tanfovy, cams) != GSR_OK) return GSR_EINVAL;
+  if (set_cams(sc, cams) != GSR_OK) return GSR_EINVAL;
   SegInfo inst;
   long long total = 0;
   if (inst_segments(V, K, inst, &total) != GSR_OK) return GSR_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  GeomState g = GeomState::carve((void*)geom, V, P, nullptr);
+  GeomState g = GeomState::carve(state->geom, V, P, nullptr);
   const TilePack tp = set_tile_pack(P, width, height);
-  BinningState b = BinningState::carve((void*)binning, V, total, inst.blk[V], !tp.packed, nullptr);
+  BinningState b = BinningState::carve(state->binning, V, total, inst.blk[V], !tp.packed, nullptr);
   // (the checkpoints, carved last, exist when the forward split: split_mode says so on the device)
-  ImageState img = ImageState::carve((void*)image, V, width, height, nullptr, true);
+  ImageState img = ImageState::carve(state->image, V, width, height, nullptr, true);
   const int gx = div_up(width, GSR_TILE_X), gy = div_up(height, GSR_TILE_Y);
   const size_t HW = (size_t)width * height;
   const int tres = tile_sort_result(width, height);
   const uint32_t* sorted = tp.packed ? b.key[tres] : b.val[tres];
-  GaussBackwardArgs a = shared_args(P, degree, M, means3D, scales, scale_modifier, rotations, shs, cov3D_precomp,
-                                     dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
-                                     dL_drotations);
-  if (accumulate != 0 && cov3D_precomp == nullptr && dL_dcov3D == nullptr)
+  GaussBackwardArgs a = shared_args(sc, gr);
+  if (gr.accumulate != 0 && sc.cov3D_precomp == nullptr && dL_dcov3D == nullptr)
     return fail(GSR_EINVAL, "%s", "accumulate needs dL_dcov3D: it carries the running dL/dcov3D between calls");
-  if (work_bytes < carry_bytes(P)) return fail(GSR_EINVAL, "%s", "backward work buffer too small");
+  void* work = gr.work;
+  if (gr.work_bytes < carry_bytes(P)) return fail(GSR_EINVAL, "%s", "backward work buffer too small");
   // the running dL/dcov3D: the caller's output when given, else the end of the work buffer (at a 256-byte
   // boundary whatever work_bytes is)
-  const size_t avail = (work_bytes - carry_bytes(P)) & ~(size_t)255;
+  const size_t avail = (gr.work_bytes - carry_bytes(P)) & ~(size_t)255;
   float* carry = dL_dcov3D ? dL_dcov3D : (float*)((char*)work + avail);
-  bool first = accumulate == 0;
+  bool first = gr.accumulate == 0;
   // groups of consecutive views whose gradient rows and records fit the work buffer
   for (int g0 = 0; g0 < V;) {
     int g1 = g0;
@@ -781,10 +746,10 @@ static int set_backward(int V, int P, int degree, int M, const int* K, int width
     rs.comp = nullptr;
     rs.ccolor = color ? color + (size_t)g0 * 3 * HW : nullptr;
     rs.dcbg = dL_dbg ? dL_dbg + (size_t)g0 * HW * 3 : nullptr;
-    rs.col2 = two ? colors2 : colors_override;
+    rs.col2 = two ? gr.colors2 : colors_override;
     rs.col2_rec = g.drange + 130;
     rs.out_col2 = nullptr;
-    rs.dpix2 = two ? dL_dcolor2 + (size_t)g0 * 3 * HW : nullptr;
+    rs.dpix2 = two ? gr.dL_dcolor2 + (size_t)g0 * 3 * HW : nullptr;
     rs.order = img.order;
     // a one-colour backward of the first colour replays split chunks when the forward wrote them.  The host passes
     // the checkpoints whenever the set's size allows a split (split_fits, no environment read here: ADVICE r05) and
@@ -819,7 +784,7 @@ static int set_backward(int V, int P, int degree, int M, const int* K, int width
     va.img = img;
     va.reach = bw.reach;
     va.grow = bw.grow;
-    va.dmeans2D = dL_dmeans2D;
+    va.dmeans2D = gr.dL_dmeans2D;
     va.vrec = bw.vrec;
     AccumArgs ab;
     ab.V = g1 - g0;
@@ -829,7 +794,7 @@ static int set_backward(int V, int P, int degree, int M, const int* K, int width
     ab.reach = bw.reach;
     ab.vrec = bw.vrec;
     ab.dcov_carry = carry;
-    ab.dcolors2 = two ? dL_dcolors2 : nullptr;
+    ab.dcolors2 = two ? gr.dL_dcolors2 : nullptr;
     for (int v = g0; v < g1; ++v) {
       if (bgs[v] == nullptr) return fail(GSR_EINVAL, "%s", "null background");
       rs.inst_start[v - g0] = inst.start[v];
@@ -850,16 +815,16 @@ static int set_backward(int V, int P, int degree, int M, const int* K, int width
     {
       PhaseScope ps(GSR_PHASE_GAUSS_BWD, s);
       const bool last = g1 == V;
-      if (last && chunks.n > 0) {
+      if (last && gr.n_chunks > 0) {
         // the final sums in Gaussian ranges, an event after each (the caller's reduction of a range starts
         // while the next range is computed)
-        const int cs = grad_chunk_size(P, chunks.n);
-        for (int c = 0; c < chunks.n; ++c) {
+        const int cs = grad_chunk_size(P, gr.n_chunks);
+        for (int c = 0; c < gr.n_chunks; ++c) {
           GaussBackwardArgs ac = a;
           ac.g0 = c * cs < P ? c * cs : P;
           ac.g1 = (c + 1) * cs < P ? (c + 1) * cs : P;
           launch_gauss_backward(ac, va, ab, s);
-          if (chunks.events[c] != nullptr) GSR_HIP_CHECK(hipEventRecord((hipEvent_t)chunks.events[c], s));
+          if (gr.chunk_events[c] != nullptr) GSR_HIP_CHECK(hipEventRecord((hipEvent_t)gr.chunk_events[c], s));
         }
       } else {
         launch_gauss_backward(a, va, ab, s);
@@ -871,15 +836,6 @@ static int set_backward(int V, int P, int degree, int M, const int* K, int width
   return last_launch();
 }
 
-int gsr_set_backward_chunks(int n_chunks, void* const* events) {
-  if (n_chunks < 0 || n_chunks > GSR_GRAD_CHUNKS_MAX || (n_chunks > 0 && events == nullptr))
-    return fail(GSR_EINVAL, "%s", "bad gradient chunk request");
-  g_next_chunks = GradChunks{};
-  g_next_chunks.n = n_chunks;
-  for (int c = 0; c < n_chunks; ++c) g_next_chunks.events[c] = events[c];
-  return GSR_OK;
-}
-
 int gsr_grad_chunk_range(int P, int n_chunks, int chunk, int* g0, int* g1) {
   if (P < 0 || n_chunks < 1 || n_chunks > GSR_GRAD_CHUNKS_MAX || chunk < 0 || chunk >= n_chunks || g0 == nullptr ||
       g1 == nullptr)
@@ -888,43 +844,6 @@ int gsr_grad_chunk_range(int P, int n_chunks, int chunk, int* g0, int* g1) {
   *g0 = chunk * cs < P ? chunk * cs : P;
   *g1 = (chunk + 1) * cs < P ? (chunk + 1) * cs : P;
   return GSR_OK;
-}
-
-int gsr_set_backward(int V, int P, int degree, int M, const int* K, int width, int height, const float* const* bgs,
-                     const float* means3D, const float* scales, float scale_modifier, const float* rotations,
-                     const float* shs, const float* cov3D_precomp, const float* const* viewmatrices,
-                     const float* const* projmatrices, const float* const* campos, const float* tanfovx,
-                     const float* tanfovy, const int* radii, const void* geom, const void* binning,
-                     const void* image, const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
-                     float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D,
-                     float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations, int accumulate,
-                     void* work, size_t work_bytes, void* stream) {
-  return set_backward(V, P, degree, M, K, width, height, bgs, means3D, scales, scale_modifier, rotations, shs,
-                      cov3D_precomp, viewmatrices, projmatrices, campos, tanfovx, tanfovy, radii, geom, binning, image,
-                      dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D,
-                      dL_dsh, dL_dscales, dL_drotations, accumulate, work, work_bytes, nullptr, nullptr, nullptr,
-                      stream);
-}
-
-int gsr_set_backward_composite(int V, int P, int degree, int M, const int* K, int width, int height,
-                               const float* const* bgs, const float* means3D, const float* scales,
-                               float scale_modifier, const float* rotations, const float* shs,
-                               const float* cov3D_precomp, const float* const* viewmatrices,
-                               const float* const* projmatrices, const float* const* campos, const float* tanfovx,
-                               const float* tanfovy, const int* radii, const void* geom, const void* binning,
-                               const void* image, const float* bg_images, const float* color,
-                               const float* dL_drender, const float* dL_ddepth, const float* dL_dalpha,
-                               float* dL_dbg, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
-                               float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
-                               float* dL_drotations, int accumulate, void* work, size_t work_bytes, void* stream) {
-  // (bg_images NULL: the clamp alone; no dL_dbg then)
-  if (color == nullptr) return fail(GSR_EINVAL, "%s", "null composite argument");
-  if (bg_images == nullptr && dL_dbg != nullptr) return fail(GSR_EINVAL, "%s", "dL_dbg needs bg_images");
-  return set_backward(V, P, degree, M, K, width, height, bgs, means3D, scales, scale_modifier, rotations, shs,
-                      cov3D_precomp, viewmatrices, projmatrices, campos, tanfovx, tanfovy, radii, geom, binning, image,
-                      dL_drender, dL_ddepth, dL_dalpha, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D,
-                      dL_dsh, dL_dscales, dL_drotations, accumulate, work, work_bytes, bg_images, color, dL_dbg,
-                      stream);
 }
 
 // ---- one view (the reference's per-call interface): a set of one --------------------------
@@ -939,54 +858,8 @@ size_t gsr_binning_bytes(int K, int width, int height) {
   BinningState::carve(nullptr, 1, total, seg.blk[1], true, &b);
   return b;
 }
-size_t gsr_image_bytes(int width, int height) { return gsr_set_image_bytes(1, width, height); }
-int gsr_set_backward_colors(int V, int P, const int* K, int width, int height, const float* const* bgs,
-                            const float* means3D, const float* scales, float scale_modifier, const float* rotations,
-                            const float* cov3D_precomp, const float* const* viewmatrices,
-                            const float* const* projmatrices, const float* const* campos, const float* tanfovx,
-                            const float* tanfovy, const int* radii, const void* geom, const void* binning,
-                            const void* image, const float* colors, const float* dL_dcolor, float* dL_dmeans2D,
-                            float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D,
-                            float* dL_dscales, float* dL_drotations, int accumulate, void* work, size_t work_bytes,
-                            void* stream) {
-  if (colors == nullptr) return fail(GSR_EINVAL, "%s", "null colours");
-  return set_backward(V, P, 0, 0, K, width, height, bgs, means3D, scales, scale_modifier, rotations, nullptr,
-                      cov3D_precomp, viewmatrices, projmatrices, campos, tanfovx, tanfovy, radii, geom, binning, image,
-                      dL_dcolor, nullptr, nullptr, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, nullptr,
-                      dL_dscales, dL_drotations, accumulate, work, work_bytes, nullptr, nullptr, nullptr, stream, colors);
-}
-
-size_t gsr_backward_bytes(int P, int K) { return gsr_set_backward_bytes(1, P, &K); }
-
-size_t gsr_set_backward_two_colors_bytes(int V, int P, const int* K) {
-  long long total = 0;
-  for (int v = 0; v < V; ++v) total += K[v];
-  return BackwardState::bytes_for(total, V, P, true) + carry_bytes(P);
-}
-
-int gsr_set_backward_two_colors(int V, int P, int degree, int M, const int* K, int width, int height,
-                                const float* const* bgs, const float* means3D, const float* scales,
-                                float scale_modifier, const float* rotations, const float* shs,
-                                const float* cov3D_precomp, const float* const* viewmatrices,
-                                const float* const* projmatrices, const float* const* campos, const float* tanfovx,
-                                const float* tanfovy, const int* radii, const void* geom, const void* binning,
-                                const void* image, const float* bg_images, const float* color,
-                                const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
-                                float* dL_dbg, const float* colors2, const float* dL_dcolor2, float* dL_dmeans2D,
-                                float* dL_dcolors, float* dL_dcolors2, float* dL_dopacity, float* dL_dmeans3D,
-                                float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
-                                int accumulate, void* work, size_t work_bytes, void* stream) {
-  if (colors2 == nullptr || dL_dcolor2 == nullptr || dL_dcolors2 == nullptr)
-    return fail(GSR_EINVAL, "%s", "null second colour argument");
-  // (color without bg_images: the clamp alone; neither: no composite)
-  if (bg_images != nullptr && color == nullptr) return fail(GSR_EINVAL, "%s", "composite needs the forward's color");
-  if (bg_images == nullptr && dL_dbg != nullptr) return fail(GSR_EINVAL, "%s", "dL_dbg needs bg_images");
-  return set_backward(V, P, degree, M, K, width, height, bgs, means3D, scales, scale_modifier, rotations, shs,
-                      cov3D_precomp, viewmatrices, projmatrices, campos, tanfovx, tanfovy, radii, geom, binning, image,
-                      dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D,
-                      dL_dsh, dL_dscales, dL_drotations, accumulate, work, work_bytes, bg_images, color, dL_dbg,
-                      stream, nullptr, colors2, dL_dcolor2, dL_dcolors2);
-}
+size_t gsr_image_bytes(int width, int height) { return gsr_set_image_bytes(1, 0, nullptr, width, height, 0); }
+size_t gsr_backward_bytes(int P, int K) { return gsr_set_backward_bytes(1, P, &K, 0); }
 
 int gsr_forward_preprocess(int P, int degree, int M, const float* means3D, const float* scales,
                            float scale_modifier, const float* rotations, const float* opacities,
@@ -994,20 +867,28 @@ int gsr_forward_preprocess(int P, int degree, int M, const float* means3D, const
                            const float* viewmatrix, const float* projmatrix, const float* campos,
                            int width, int height, float tanfovx, float tanfovy, int prefiltered,
                            int* radii, void* geom, void* stream) {
-  return gsr_set_preprocess(1, P, degree, M, means3D, scales, scale_modifier, rotations, opacities, shs,
-                            colors_precomp, cov3D_precomp, &viewmatrix, &projmatrix, &campos, &tanfovx, &tanfovy,
-                            width, height, prefiltered, radii, geom, stream);
+  // (host arrays of one: the arguments themselves)
+  const gsr_set_scene sc{1, P, degree, M, width, height, prefiltered, scale_modifier, means3D, scales, rotations,
+                         opacities, shs, colors_precomp, cov3D_precomp, &viewmatrix, &projmatrix, &campos, nullptr,
+                         &tanfovx, &tanfovy};
+  const gsr_set_state st{radii, geom, nullptr, nullptr, nullptr};
+  return gsr_set_preprocess(&sc, &st, nullptr, stream);
 }
 
 int gsr_num_rendered(const void* geom, int P, int* num_rendered, int* num_visible, void* stream) {
-  return gsr_set_num_rendered(1, geom, P, num_rendered, num_visible, stream);
+  return gsr_set_num_rendered(1, geom, P, num_rendered, num_visible, nullptr, stream);
 }
 
 int gsr_forward_render(int P, int K, int width, int height, const float* bg, void* geom,
                        void* binning, void* image, float* out_color, float* out_depth,
                        float* out_alpha, void* stream) {
   if (K < 0) return fail(GSR_EINVAL, "%s", "bad sizes");
-  return gsr_set_render(1, P, &K, width, height, &bg, geom, binning, image, out_color, out_depth, out_alpha, stream);
+  gsr_set_scene sc{};
+  sc.V = 1, sc.P = P, sc.width = width, sc.height = height, sc.bgs = &bg;
+  const gsr_set_state st{nullptr, geom, binning, image, &K};
+  gsr_set_outputs o{};
+  o.out_color = out_color, o.out_depth = out_depth, o.out_alpha = out_alpha;
+  return gsr_set_render(&sc, &st, &o, stream);
 }
 
 int gsr_backward(int P, int degree, int M, int K, int width, int height, const float* bg,
@@ -1020,13 +901,19 @@ int gsr_backward(int P, int degree, int M, int K, int width, int height, const f
                  float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D,
                  float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
                  void* work, void* stream) {
-  (void)opacities;
-  (void)colors_precomp;
   if (K < 0) return fail(GSR_EINVAL, "%s", "bad sizes");
-  return gsr_set_backward(1, P, degree, M, &K, width, height, &bg, means3D, scales, scale_modifier, rotations, shs,
-                          cov3D_precomp, &viewmatrix, &projmatrix, &campos, &tanfovx, &tanfovy, radii, geom, binning,
-                          image, dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D,
-                          dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, 0, work, gsr_backward_bytes(P, K), stream);
+  const gsr_set_scene sc{1, P, degree, M, width, height, 0, scale_modifier, means3D, scales, rotations,
+                         opacities, shs, colors_precomp, cov3D_precomp, &viewmatrix, &projmatrix, &campos, &bg,
+                         &tanfovx, &tanfovy};
+  // (the backward only reads the forward state)
+  const gsr_set_state st{(int*)radii, (void*)geom, (void*)binning, (void*)image, &K};
+  gsr_set_grads gr{};
+  gr.dL_dcolor = dL_dcolor, gr.dL_ddepth = dL_ddepth, gr.dL_dalpha = dL_dalpha;
+  gr.dL_dmeans2D = dL_dmeans2D, gr.dL_dcolors = dL_dcolors, gr.dL_dopacity = dL_dopacity;
+  gr.dL_dmeans3D = dL_dmeans3D, gr.dL_dcov3D = dL_dcov3D, gr.dL_dsh = dL_dsh;
+  gr.dL_dscales = dL_dscales, gr.dL_drotations = dL_drotations;
+  gr.work = work, gr.work_bytes = gsr_backward_bytes(P, K);
+  return gsr_set_backward(&sc, &st, &gr, stream);
 }
 
 int gsr_profile_enable(int enable) {

@@ -30,6 +30,40 @@ _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
 _sz = ctypes.c_size_t
+_P = ctypes.POINTER
+_ip, _fp, _vpp = _P(_i), _P(_f), _P(_vp)
+
+
+def _fields(ctype, names):
+    return [(n, ctype) for n in names.split()]
+
+
+# The argument structs of the view-set calls: field for field those of include/gsr.h (tests/test_abi.py compares the
+# names, offsets and sizes with the header's through the C compiler).  A struct holds addresses only: whoever fills
+# one keeps the tensors and host arrays behind them alive.
+class SetScene(ctypes.Structure):
+    _fields_ = (_fields(_i, "V P degree M width height prefiltered") + [("scale_modifier", _f)]
+                + _fields(_vp, "means3D scales rotations opacities shs colors_precomp cov3D_precomp")
+                + _fields(_vpp, "viewmatrices projmatrices campos bgs") + _fields(_fp, "tanfovx tanfovy"))
+
+
+class SetState(ctypes.Structure):
+    _fields_ = _fields(_vp, "radii geom binning image") + [("num_rendered", _ip)]
+
+
+class SetOutputs(ctypes.Structure):
+    _fields_ = _fields(_vp, "out_color out_depth out_alpha bg_images out_render colors2 out_color2")
+
+
+class SetGrads(ctypes.Structure):
+    _fields_ = (_fields(_vp, "dL_dcolor dL_ddepth dL_dalpha color bg_images dL_dbg colors_override colors2 dL_dcolor2 "
+                             "dL_dcolors2 dL_dmeans2D dL_dcolors dL_dopacity dL_dmeans3D dL_dcov3D dL_dsh dL_dscales "
+                             "dL_drotations")
+                + [("accumulate", _i), ("work", _vp), ("work_bytes", _sz), ("n_chunks", _i), ("chunk_events", _vpp)])
+
+
+STRUCTS = {"gsr_set_scene": SetScene, "gsr_set_state": SetState, "gsr_set_outputs": SetOutputs,
+           "gsr_set_grads": SetGrads}
 
 # name -> (restype, argtypes); must match include/gsr.h exactly (checked by tests/test_abi.py)
 SIGNATURES = {
@@ -71,52 +105,14 @@ SIGNATURES = {
     "gsr_knn_points": (_i, [_i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gsr_set_geom_bytes": (_sz, [_i, _i]),
     "gsr_set_binning_bytes": (_sz, [_i, _i, ctypes.POINTER(_i), _i, _i]),
-    "gsr_set_image_bytes": (_sz, [_i, _i, _i]),
-    "gsr_set_image_bytes_ex": (_sz, [_i, _i, ctypes.POINTER(_i), _i, _i, _i]),
+    "gsr_set_image_bytes": (_sz, [_i, _i, _ip, _i, _i, _i]),
     "gsr_profile_kernel": (ctypes.c_char_p, [_i]),
-    "gsr_set_backward_bytes": (_sz, [_i, _i, ctypes.POINTER(_i)]),
-    "gsr_set_preprocess": (
-        _i,
-        [_i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp] + [ctypes.POINTER(_vp)] * 3
-        + [ctypes.POINTER(_f)] * 2 + [_i, _i, _i, _vp, _vp, _vp],
-    ),
-    "gsr_set_preprocess_ex": (
-        _i,
-        [_i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp] + [ctypes.POINTER(_vp)] * 3
-        + [ctypes.POINTER(_f)] * 2 + [_i, _i, _i, _vp, _vp, _vp, _vp],
-    ),
-    "gsr_set_num_rendered": (_i, [_i, _vp, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), _vp]),
-    "gsr_set_num_rendered_ex": (_i, [_i, _vp, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _vp]),
+    "gsr_set_backward_bytes": (_sz, [_i, _i, _ip, _i]),
+    "gsr_set_preprocess": (_i, [_P(SetScene), _P(SetState), _vp, _vp]),
+    "gsr_set_num_rendered": (_i, [_i, _vp, _i, _ip, _ip, _ip, _vp]),
     "gsr_set_gauss_state": (_i, [_i, _vp, _i, _vp, _vp, _vp]),
-    "gsr_set_render": (_i, [_i, _i, ctypes.POINTER(_i), _i, _i, ctypes.POINTER(_vp)] + [_vp] * 7),
-    "gsr_set_backward": (
-        _i,
-        [_i, _i, _i, _i, ctypes.POINTER(_i), _i, _i, ctypes.POINTER(_vp), _vp, _vp, _f, _vp, _vp, _vp]
-        + [ctypes.POINTER(_vp)] * 3 + [ctypes.POINTER(_f)] * 2 + [_vp] * 4 + [_vp] * 3 + [_vp] * 8
-        + [_i, _vp, _sz, _vp],
-    ),
-    "gsr_set_render_composite": (_i, [_i, _i, ctypes.POINTER(_i), _i, _i, ctypes.POINTER(_vp)] + [_vp] * 9),
-    "gsr_set_backward_composite": (
-        _i,
-        [_i, _i, _i, _i, ctypes.POINTER(_i), _i, _i, ctypes.POINTER(_vp), _vp, _vp, _f, _vp, _vp, _vp]
-        + [ctypes.POINTER(_vp)] * 3 + [ctypes.POINTER(_f)] * 2 + [_vp] * 4 + [_vp] * 6 + [_vp] * 8
-        + [_i, _vp, _sz, _vp],
-    ),
-    "gsr_set_render_two_colors": (_i, [_i, _i, ctypes.POINTER(_i), _i, _i, ctypes.POINTER(_vp)] + [_vp] * 11),
-    "gsr_set_backward_two_colors_bytes": (_sz, [_i, _i, ctypes.POINTER(_i)]),
-    "gsr_set_backward_two_colors": (
-        _i,
-        [_i, _i, _i, _i, ctypes.POINTER(_i), _i, _i, ctypes.POINTER(_vp), _vp, _vp, _f, _vp, _vp, _vp]
-        + [ctypes.POINTER(_vp)] * 3 + [ctypes.POINTER(_f)] * 2 + [_vp] * 4 + [_vp] * 8 + [_vp] * 9
-        + [_i, _vp, _sz, _vp],
-    ),
-    "gsr_set_backward_colors": (
-        _i,
-        [_i, _i, ctypes.POINTER(_i), _i, _i, ctypes.POINTER(_vp), _vp, _vp, _f, _vp, _vp]
-        + [ctypes.POINTER(_vp)] * 3 + [ctypes.POINTER(_f)] * 2 + [_vp] * 4 + [_vp] * 2 + [_vp] * 7
-        + [_i, _vp, _sz, _vp],
-    ),
-    "gsr_set_backward_chunks": (_i, [_i, ctypes.POINTER(_vp)]),
+    "gsr_set_render": (_i, [_P(SetScene), _P(SetState), _P(SetOutputs), _vp]),
+    "gsr_set_backward": (_i, [_P(SetScene), _P(SetState), _P(SetGrads), _vp]),
     "gsr_grad_chunk_range": (_i, [_i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "gsr_profile_enable": (_i, [_i]),
     "gsr_profile_read": (_i, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong), _i]),
@@ -159,7 +155,7 @@ def host_trace_read(reset: bool = True) -> dict:
     return out
 
 
-ABI_VERSION = 6  # include/gsr.h GSR_ABI_VERSION this binding is written against
+ABI_VERSION = 7  # include/gsr.h GSR_ABI_VERSION this binding is written against
 
 
 def load_library(path: str | None = None):
@@ -288,7 +284,7 @@ def rasterize_gaussians(bg, means3D, colors, opacity, scales, rotations, scale_m
         LAST_GEOM = geom
     binning = torch.empty(int(lib.gsr_binning_bytes(num_rendered, W, H)), **u8)
     # sized for this forward's split decision (no split checkpoints unless the forward writes them)
-    image = torch.empty(int(lib.gsr_set_image_bytes_ex(1, P, (ctypes.c_int * 1)(num_rendered), W, H, 0)), **u8)
+    image = torch.empty(int(lib.gsr_set_image_bytes(1, P, (ctypes.c_int * 1)(num_rendered), W, H, 0)), **u8)
     _check(lib.gsr_forward_render(P, num_rendered, W, H, _ptr(bg), _ptr(geom), _ptr(binning), _ptr(image),
                                   _ptr(out_color), _ptr(out_depth), _ptr(out_alpha), stream))
     return num_rendered, out_color, out_depth, out_alpha, radii, geom, binning, image

@@ -35,30 +35,41 @@ def _ptrs(ts):
     return _arr(ctypes.c_void_p, [t.data_ptr() for t in ts])
 
 
-class _ViewSet:
-    """Forward state of one set of views."""
+def _addr(t):
+    """The device address of a tensor for a struct field (None: NULL)."""
+    return None if t is None or t.numel() == 0 else t.data_ptr()
 
-    def __init__(self, lo, hi, cams, tanx, tany):
+
+class _ViewSet:
+    """Forward state of one set of views: the scene and state structs of include/gsr.h, built once in the forward
+    and reused by the backward, and the Python objects whose addresses they hold."""
+
+    def __init__(self, lo, hi, cams, tanx, tany, gaussians, radii, **shared):
         self.lo, self.hi = lo, hi
-        self.cams = cams  # [(view, proj, campos, bg)] contiguous fp32 device tensors
-        self.tanx, self.tany = tanx, tany
+        # [(view, proj, campos, bg)], the Gaussians' arrays and the set's rows of radii: contiguous fp32 / int32
+        # device tensors, kept alive with the structs that point at them
+        self.cams, self.gaussians, self.radii = cams, gaussians, radii
         self.K = None
         self.geom = self.binning = self.image = None
-        # the host arrays the C ABI takes, built once for the forward and the backward
-        self.arrays = (_ptrs([c[0] for c in cams]), _ptrs([c[1] for c in cams]), _ptrs([c[2] for c in cams]),
-                       _arr(ctypes.c_float, tanx), _arr(ctypes.c_float, tany))
-        self.bgs = _ptrs([c[3] for c in cams])
-        self.Karr = None
+        self.scene = _C.SetScene(
+            V=hi - lo, viewmatrices=_ptrs([c[0] for c in cams]), projmatrices=_ptrs([c[1] for c in cams]),
+            campos=_ptrs([c[2] for c in cams]), bgs=_ptrs([c[3] for c in cams]),
+            tanfovx=_arr(ctypes.c_float, tanx), tanfovy=_arr(ctypes.c_float, tany), **shared,
+            **{name: _addr(t) for name, t in gaussians.items()})
+        self.state = _C.SetState(radii=_addr(radii))
 
     @property
     def V(self):
         return self.hi - self.lo
 
-    def cam_arrays(self):
-        return self.arrays
+    def allocate(self, **buffers):
+        """Keep the set's geom / binning / image buffers and point the state at them."""
+        for name, t in buffers.items():
+            setattr(self, name, t)
+            setattr(self.state, name, _addr(t))
 
 
-# A two-colour forward hands colors2 to the preprocess too (gsr_set_preprocess_ex), which writes each Gaussian's
+# A two-colour forward hands colors2 to the preprocess too (gsr_set_preprocess), which writes each Gaussian's
 # second colour into the record it writes anyway; the blends then read it from the record's line.  False: the
 # blends gather colors2 apart (the same bits; tests/test_gpu_configs.py compares the two).
 EMBED_COLORS2 = True
@@ -107,51 +118,47 @@ class _RasterizeViews(torch.autograd.Function):
             color2 = torch.empty((V, 3, H, W), **fopt)
         radii = torch.empty((V, P), dtype=torch.int32, device=dev)
         sets = []
+        gaussians = dict(means3D=m3, scales=sc, rotations=rot, opacities=op, shs=shc, colors_precomp=col,
+                         cov3D_precomp=c3)
         for lo in range(0, V, SET_MAX):
             hi = min(V, lo + SET_MAX)
             cams = [(f(s.viewmatrix, "viewmatrix"), f(s.projmatrix, "projmatrix"), f(s.campos, "campos"),
                      f(s.bg, "bg")) for s in settings_list[lo:hi]]
             vs = _ViewSet(lo, hi, cams, [float(s.tanfovx) for s in settings_list[lo:hi]],
-                          [float(s.tanfovy) for s in settings_list[lo:hi]])
-            vs.geom = torch.empty(int(lib.gsr_set_geom_bytes(vs.V, P)), dtype=torch.uint8, device=dev)
-            views, projs, campos, tx, ty = vs.cam_arrays()
+                          [float(s.tanfovy) for s in settings_list[lo:hi]], gaussians, radii[lo:hi], P=P,
+                          degree=int(s0.sh_degree), M=M, width=W, height=H, prefiltered=int(bool(s0.prefiltered)),
+                          scale_modifier=float(s0.scale_modifier))
+            vs.allocate(geom=torch.empty(int(lib.gsr_set_geom_bytes(vs.V, P)), dtype=torch.uint8, device=dev))
             t0 = _C.host_mark("fwd_setup", t0)
             # (the second colour set, when there is one, rides in the records the preprocess writes: the two-colour
             # blends then read it with the record instead of gathering it apart)
-            _C._check(lib.gsr_set_preprocess_ex(
-                vs.V, P, int(s0.sh_degree), M, p(m3), p(sc), float(s0.scale_modifier), p(rot), p(op), p(shc), p(col),
-                p(c3), views, projs, campos, tx, ty, W, H, int(bool(s0.prefiltered)), p(radii[lo:hi]), p(vs.geom),
-                p(c2) if c2 is not None and EMBED_COLORS2 else None, stream))
+            _C._check(lib.gsr_set_preprocess(vs.scene, vs.state, p(c2) if c2 is not None and EMBED_COLORS2 else None,
+                                             stream))
             sets.append(vs)
             t0 = _C.host_mark("fwd_preprocess_launch", t0)
         for vs in sets:
             K = (ctypes.c_int * vs.V)()
             L = (ctypes.c_int * vs.V)()
             # the reference's one host sync: the instance counts size the binning buffers
-            _C._check(lib.gsr_set_num_rendered_ex(vs.V, p(vs.geom), P, K, None, L, stream))
+            _C._check(lib.gsr_set_num_rendered(vs.V, p(vs.geom), P, K, None, L, stream))
             t0 = _C.host_mark("fwd_sync_wait", t0)
             vs.K = list(K)
             _C.RECENT_LISTED.extend(L)
             _C.RECENT_FORWARDS.extend((k, H, W) for k in vs.K)
-            Karr = vs.Karr = _arr(ctypes.c_int, vs.K)
-            vs.binning = torch.empty(int(lib.gsr_set_binning_bytes(vs.V, P, Karr, W, H)), dtype=torch.uint8, device=dev)
-            vs.image = torch.empty(int(lib.gsr_set_image_bytes_ex(vs.V, P, Karr, W, H, int(c2 is not None))),
-                                   dtype=torch.uint8, device=dev)
+            vs.state.num_rendered = K
+            vs.allocate(
+                binning=torch.empty(int(lib.gsr_set_binning_bytes(vs.V, P, K, W, H)), dtype=torch.uint8, device=dev),
+                image=torch.empty(int(lib.gsr_set_image_bytes(vs.V, P, K, W, H, int(c2 is not None))),
+                                  dtype=torch.uint8, device=dev))
             sl = slice(vs.lo, vs.hi)
+            out = _C.SetOutputs(out_color=_addr(color[sl]), out_depth=_addr(depth[sl]), out_alpha=_addr(alpha[sl]))
+            if cbg is not None:
+                out.bg_images = _addr(cbg[sl])
+            if fused_out:
+                out.out_render = _addr(render[sl])
             if c2 is not None:
-                _C._check(lib.gsr_set_render_two_colors(
-                    vs.V, P, Karr, W, H, vs.bgs, p(vs.geom), p(vs.binning), p(vs.image),
-                    p(color[sl]), p(depth[sl]), p(alpha[sl]), p(cbg[sl]) if cbg is not None else None,
-                    p(render[sl]) if fused_out else None, p(c2), p(color2[sl]), stream))
-            elif not fused_out:
-                _C._check(lib.gsr_set_render(vs.V, P, Karr, W, H, vs.bgs, p(vs.geom),
-                                             p(vs.binning), p(vs.image), p(color[sl]), p(depth[sl]), p(alpha[sl]),
-                                             stream))
-            else:
-                _C._check(lib.gsr_set_render_composite(
-                    vs.V, P, Karr, W, H, vs.bgs, p(vs.geom), p(vs.binning), p(vs.image),
-                    p(color[sl]), p(depth[sl]), p(alpha[sl]), p(cbg[sl]) if cbg is not None else None,
-                    p(render[sl]), stream))
+                out.colors2, out.out_color2 = _addr(c2), _addr(color2[sl])
+            _C._check(lib.gsr_set_render(vs.scene, vs.state, out, stream))
             t0 = _C.host_mark("fwd_render_launch", t0)
         ctx.settings = settings_list
         ctx.grad_reduce = grad_reduce
@@ -213,71 +220,55 @@ class _RasterizeViews(torch.autograd.Function):
             gd = g_depth.float().contiguous() if g_depth is not None else None
             ga = g_alpha.float().contiguous() if g_alpha is not None else None
             stream = _C._stream(dev)
-            p = _C._ptr
-            # both calls of a two-colour forward in one backward pass (gsr_set_backward_two_colors);
+            # both calls of a two-colour forward in one backward pass (the colors2 fields of gsr_set_grads);
             # two_color_backward="separate" runs the second call's backward after the first's instead
             fused2 = second and ctx.two_color_bwd != "separate"
-            if fused2:
+            if second:
                 g2 = g_color2.float().contiguous()
             reducer = ctx.grad_reduce if ctx.grad_reduce is not None and ctx.grad_reduce.active() else None
             # per-range events only when the last set's call is the last writer of the per-Gaussian sums: with
             # the second colour's backward run separately after it (two_color_backward="separate"), that call
             # adds into the same gradients, so the reduction waits for the whole stream instead
             events = reducer.chunk_events(dev) if reducer is not None and (fused2 or not second) else None
+            # what every call of this backward shares; the per-set fields are assigned in the loop
+            shared = dict(dL_dopacity=_addr(d_op), dL_dmeans3D=_addr(d_m3), dL_dcov3D=_addr(d_c3),
+                          dL_dscales=_addr(d_sc), dL_drotations=_addr(d_rot))
+            g = _C.SetGrads(dL_dcolors=_addr(d_col), dL_dsh=_addr(d_sh), **shared)
+            if fused2:
+                g.colors2, g.dL_dcolors2 = _addr(c2), _addr(d_c2)
             for si, vs in enumerate(ctx.sets):
                 if events is not None and si == len(ctx.sets) - 1:
                     # the last set's call forms the final per-Gaussian sums: in ranges, an event after each
-                    _C._check(lib.gsr_set_backward_chunks(
-                        len(events), _arr(ctypes.c_void_p, [e.cuda_event for e in events])))
-                Karr = vs.Karr
+                    g.n_chunks, g.chunk_events = len(events), _arr(ctypes.c_void_p, [e.cuda_event for e in events])
                 # (the scratch grows with K: the largest single view bounds what a view group needs)
                 kmax = _arr(ctypes.c_int, [max(vs.K)])
-                if fused2:
-                    need = int(lib.gsr_set_backward_two_colors_bytes(vs.V, P, Karr))
-                    largest = int(lib.gsr_set_backward_two_colors_bytes(1, P, kmax))
-                else:
-                    need = int(lib.gsr_set_backward_bytes(vs.V, P, Karr))
-                    largest = int(lib.gsr_set_backward_bytes(1, P, kmax))
+                need = int(lib.gsr_set_backward_bytes(vs.V, P, vs.state.num_rendered, int(fused2)))
+                largest = int(lib.gsr_set_backward_bytes(1, P, kmax, int(fused2)))
                 work = torch.empty(max(largest, min(need, WORK_BUDGET)), dtype=torch.uint8, device=dev)
-                views, projs, campos, tx, ty = vs.cam_arrays()
                 sl = slice(vs.lo, vs.hi)
-                gdp = p(gd[sl]) if gd is not None else None
-                gap = p(ga[sl]) if ga is not None else None
+                g.dL_dcolor, g.dL_dmeans2D = _addr(gc[sl]), _addr(d_m2[sl])
+                g.dL_ddepth = _addr(gd[sl]) if gd is not None else None
+                g.dL_dalpha = _addr(ga[sl]) if ga is not None else None
+                # (a forward with a fused clamp or composite: gc is dL/drender, masked by the forward's colour)
+                g.color = _addr(color[sl]) if color is not None else None
+                g.bg_images = _addr(cbg[sl]) if cbg is not None else None
+                g.dL_dbg = _addr(d_bg[sl]) if d_bg is not None else None
                 if fused2:
-                    _C._check(lib.gsr_set_backward_two_colors(
-                        vs.V, P, int(s0.sh_degree), M, Karr, W, H, vs.bgs, p(m3), p(sc),
-                        float(s0.scale_modifier), p(rot), p(shc), p(c3), views, projs, campos, tx, ty, p(radii[sl]),
-                        p(vs.geom), p(vs.binning), p(vs.image), p(cbg[sl]) if cbg is not None else None,
-                        p(color[sl]) if color is not None else None, p(gc[sl]), gdp, gap,
-                        p(d_bg[sl]) if d_bg is not None else None, p(c2), p(g2[sl]), p(d_m2[sl]), p(d_col), p(d_c2),
-                        p(d_op), p(d_m3), p(d_c3), p(d_sh), p(d_sc), p(d_rot), 1 if si > 0 else 0, p(work),
-                        work.numel(), stream))
-                    continue
-                if color is None:
-                    _C._check(lib.gsr_set_backward(
-                        vs.V, P, int(s0.sh_degree), M, Karr, W, H, vs.bgs, p(m3), p(sc),
-                        float(s0.scale_modifier), p(rot), p(shc), p(c3), views, projs, campos, tx, ty, p(radii[sl]),
-                        p(vs.geom), p(vs.binning), p(vs.image), p(gc[sl]), gdp, gap, p(d_m2[sl]), p(d_col), p(d_op),
-                        p(d_m3), p(d_c3), p(d_sh), p(d_sc), p(d_rot), 1 if si > 0 else 0, p(work), work.numel(),
-                        stream))
-                else:
-                    _C._check(lib.gsr_set_backward_composite(
-                        vs.V, P, int(s0.sh_degree), M, Karr, W, H, vs.bgs, p(m3), p(sc),
-                        float(s0.scale_modifier), p(rot), p(shc), p(c3), views, projs, campos, tx, ty, p(radii[sl]),
-                        p(vs.geom), p(vs.binning), p(vs.image), p(cbg[sl]) if cbg is not None else None,
-                        p(color[sl]), p(gc[sl]), gdp, gap,
-                        p(d_bg[sl]) if d_bg is not None else None, p(d_m2[sl]), p(d_col), p(d_op), p(d_m3), p(d_c3),
-                        p(d_sh), p(d_sc), p(d_rot), 1 if si > 0 else 0, p(work), work.numel(), stream))
-                if second:
-                    # the second call's backward on the shared forward state (its screen-space gradient
-                    # is discarded, as the reference's fresh zero means2D of that call is)
-                    g2 = g_color2.float().contiguous()
+                    g.dL_dcolor2 = _addr(g2[sl])
+                g.accumulate = 1 if si > 0 else 0
+                g.work, g.work_bytes = _addr(work), work.numel()
+                _C._check(lib.gsr_set_backward(vs.scene, vs.state, g, stream))
+                if second and not fused2:
+                    # the second call's backward on the shared forward state: precomputed colours, so a scene
+                    # without SHs (its screen-space gradient is discarded, as the reference's fresh zero means2D
+                    # of that call is)
+                    scene2 = _C.SetScene.from_buffer_copy(vs.scene)
+                    scene2.shs = None
                     m2_scratch = torch.empty((vs.V, P, 3), **fopt)
-                    _C._check(lib.gsr_set_backward_colors(
-                        vs.V, P, Karr, W, H, vs.bgs, p(m3), p(sc), float(s0.scale_modifier),
-                        p(rot), p(c3), views, projs, campos, tx, ty, p(radii[sl]), p(vs.geom), p(vs.binning),
-                        p(vs.image), p(c2), p(g2[sl]), p(m2_scratch), p(d_c2), p(d_op), p(d_m3), p(d_c3), p(d_sc),
-                        p(d_rot), 1, p(work), work.numel(), stream))
+                    _C._check(lib.gsr_set_backward(scene2, vs.state, _C.SetGrads(
+                        colors_override=_addr(c2), dL_dcolor=_addr(g2[sl]), dL_dmeans2D=_addr(m2_scratch),
+                        dL_dcolors=_addr(d_c2), accumulate=1, work=_addr(work), work_bytes=work.numel(), **shared),
+                        stream))
         if d_bg is not None:
             d_bg = d_bg.reshape(ctx.bg_shape)
         if getattr(ctx, "needs_c3_scratch", False):
@@ -316,7 +307,7 @@ def rasterize_views(settings_list, means3D, means2D_list, opacities, shs=None, c
     colors2 (P, 3): a second rasterizer call that differs only in its colours — the SuGaR normal renderer's
     ``rasterizer(..., means2D=zeros_like(means2D), shs=None, colors_precomp=pc.get_gs_normals, ...)``
     (renderer/diff_sugar_rasterizer_normal.py:182-191) — rendered from the same geometry, sorts and blend
-    weights (include/gsr.h gsr_set_render_two_colors); a fifth output holds its colour image (V, 3, H, W).
+    weights (include/gsr.h gsr_set_outputs.colors2); a fifth output holds its colour image (V, 3, H, W).
     Its backward adds that call's parameter gradients (colors2 receives its colour gradient); its
     screen-space gradient is not added to means2D, as in the reference.
 

@@ -264,7 +264,7 @@ class ChunkedGradReduce:
     forms them.
 
     Passed to ``batched.rasterize_views(..., grad_reduce=...)``.  The backward then forms its final
-    per-Gaussian sums in `n_chunks` Gaussian ranges (include/gsr.h gsr_set_backward_chunks) with an event after
+    per-Gaussian sums in `n_chunks` Gaussian ranges (include/gsr.h gsr_set_grads.n_chunks) with an event after
     each; a communication stream waits on range c's event and all-reduces that range's rows of every
     parameter gradient (one grouped RCCL call per range) while the later ranges are computed; the launch stream
     then waits for the communication stream (GPU-side, no host block) before autograd hands the gradients to
