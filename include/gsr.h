@@ -67,8 +67,10 @@ const char* gsr_version(void);
  *   7  the view-set calls take argument structs (gsr_set_scene / _state / _outputs / _grads): one gsr_set_render and
  *      one gsr_set_backward, their variants selected by fields; the _ex, _composite, _colors, _two_colors and
  *      _chunks entry points of revisions 2-5 are gone.
+ *   8  gsr_sugar_field_workspace_bytes / gsr_sugar_field_forward / gsr_sugar_field_backward (the SuGaR regulariser's
+ *      neighbour density field and its deterministic backward).
  */
-#define GSR_ABI_VERSION 7
+#define GSR_ABI_VERSION 8
 int gsr_abi_version(void);
 /* Message of the last failing call on this thread ("" if none). */
 const char* gsr_last_error(void);
@@ -425,6 +427,56 @@ int gsr_knn_mean_dist(int P, const float* points, float* mean_dist, void* worksp
 size_t gsr_knn_points_workspace_bytes(int P, int K);
 int gsr_knn_points(int P, int K, const float* points, float* dists, long long* idx, void* workspace,
                    size_t workspace_bytes, void* stream);
+
+/*
+ * The neighbour density field of the SuGaR regulariser: replaces the gathers, the batched matmul and the sum of
+ * SuGaRRegularizer.get_field_values (utils/sugar_utils.py:296-310), the `average` beta of get_beta (:423), and the
+ * index_put scatter of their autograd backward.  M samples, K neighbour slots (1 <= K <= GSR_KNN_MAX_K), N Gaussians,
+ * M K < 2^31.  All float arrays fp32:
+ *   x (M,3) sample points;  nbr (R,K) int64 neighbour table;  row (M,) int64 or NULL;
+ *   centers (N,3);  inv_sr (N,3,3) row-major = R[i][j] / max(s[j], 1e-8), what get_covariance(return_full_matrix=True,
+ *   return_sqrt=True, inverse_scales=True) returns;  strengths (N,);  min_scale (N,) = scaling.min(-1).
+ * With row, sample m reads the table row nbr[row[m]] (the reference's knn_idx[gaussian_idx], R = N, never gathered
+ * into an (M,K) copy); with row NULL, R must equal M and sample m reads nbr[m] (closest_gaussians_idx).
+ * For slot k with j = nbr[..][k]:
+ *   d = x_m - c_j;   w = inv_sr_j^T d;   q = clamp(w.w, 0, 1e8);   op[m,k] = density_factor strengths_j exp(-q / 2)
+ *   density[m] = sum_k op[m,k]           (raw, the reference's fields['density'])
+ *   beta_avg[m] = (sum_k min_scale_j) / K
+ * op (M,K) may be NULL (not written).  d, w, q and the exponential are evaluated in fp64 per pair and rounded to fp32
+ * once; the sums and the gradient arithmetic are fp32.
+ * Out of range: a slot whose j is outside [0, N) (the -1 padding of gsr_knn_points included) contributes nothing to
+ * any output or gradient, op = 0 there, and j is never dereferenced; beta_avg still divides by K.  A row entry
+ * outside [0, R) makes every slot of that sample such a slot: density = beta_avg = op = 0 and zero gradients.
+ * NaN coordinates: unspecified values, no out-of-bounds access.
+ * Backward: dL_ddensity (M), dL_dbeta_avg (M), dL_dop (M,K), any may be NULL (zero).  Writes in full dL_dx (M,3),
+ * dL_dcenters (N,3), dL_dinv_sr (N,3,3), dL_dstrengths (N), dL_dmin_scale (N); entries nothing contributes to are
+ * exactly 0.  The clamp's gradient is 0 where w.w > 1e8.  Every pair is recomputed from the inputs; nothing of the
+ * forward is kept.
+ * Sum orders (no atomics; every result is a pure function of the input, two calls give the same bits):
+ *   over slots (density, beta_avg, dL_dx): 16 partial sums, partial l = term l (+ term l + 16 when K > 16), terms
+ *   of absent or out-of-range slots 0; the partials are combined pairwise at distances 8, 4, 2, 1
+ *   (t[i] += t[i ^ 8], then ^ 4, ^ 2, ^ 1).
+ *   per Gaussian (the four N-sized gradients): its pairs in ascending m K + k (a stable radix sort of the pairs by
+ *   Gaussian, csrc/gsr_sort.hip); pair number i of the Gaussian goes to partial i mod L, each partial adds its pairs
+ *   in that order starting from 0, and the L partials are combined pairwise at distances L/2, ..., 2, 1.
+ *   L = 64 when M K >= 48 N, else 16.
+ * workspace: gsr_sugar_field_workspace_bytes(M, K, N) bytes of device memory (256-B aligned) for the backward:
+ * sort keys and values double-buffered (16 M K bytes), the sort's counters (M K / 16), one 64-byte record and two
+ * words per Gaussian; nothing of size 9 M K.  The forward needs gsr_sugar_field_workspace_bytes(0, K, N) (the
+ * records) only.  Kernels run on `stream`; the library allocates nothing.  M = 0 launches nothing and writes
+ * nothing (the caller zeroes the N-sized gradients of an empty batch).
+ */
+size_t gsr_sugar_field_workspace_bytes(int M, int K, int N);
+int gsr_sugar_field_forward(int M, int K, int N, int R, const float* x, const long long* nbr, const long long* row,
+                            const float* centers, const float* inv_sr, const float* strengths, const float* min_scale,
+                            float density_factor, float* density, float* beta_avg, float* op, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int gsr_sugar_field_backward(int M, int K, int N, int R, const float* x, const long long* nbr, const long long* row,
+                             const float* centers, const float* inv_sr, const float* strengths, const float* min_scale,
+                             float density_factor, const float* dL_ddensity, const float* dL_dbeta_avg,
+                             const float* dL_dop, float* dL_dx, float* dL_dcenters, float* dL_dinv_sr,
+                             float* dL_dstrengths, float* dL_dmin_scale, void* workspace, size_t workspace_bytes,
+                             void* stream);
 
 /*
  * The view-segmented stable LSD radix sort that every sort of this library runs (the depth sort, the tile sort and

@@ -492,6 +492,68 @@ int gsr_knn_points(int P, int K, const float* points, float* dists, long long* i
   return last_launch();
 }
 
+// ---- the SuGaR neighbour density field (gsr_field.hip) ---------------------------------------------
+static int field_check(int M, int K, int N, int R, const float* x, const long long* nbr, const long long* row,
+                       const float* centers, const float* inv_sr, const float* strengths, const float* min_scale,
+                       FieldCall& c) {
+  if (K < 1 || K > GSR_KNN_MAX_K) return fail(GSR_EINVAL, "%s", "K must be in 1..32");
+  if (M < 0 || N < 0 || R < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if ((long long)M * K >= (1ll << 31)) return fail(GSR_EINVAL, "%s", "M x K must stay below 2^31: split the samples");
+  if (row == nullptr && R != M) return fail(GSR_EINVAL, "%s", "without row the neighbour table has M rows");
+  if (M > 0 && (x == nullptr || (R > 0 && nbr == nullptr))) return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (N > 0 && (centers == nullptr || inv_sr == nullptr || strengths == nullptr || min_scale == nullptr))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  c = FieldCall{M, K, N, R, x, nbr, row, centers, inv_sr, strengths, min_scale, 1.0f};
+  return GSR_OK;
+}
+
+size_t gsr_sugar_field_workspace_bytes(int M, int K, int N) {
+  if (K < 1 || K > GSR_KNN_MAX_K) return 0;
+  return field_workspace_bytes(M < 0 ? 0 : M, K, N < 0 ? 0 : N);
+}
+
+int gsr_sugar_field_forward(int M, int K, int N, int R, const float* x, const long long* nbr, const long long* row,
+                            const float* centers, const float* inv_sr, const float* strengths, const float* min_scale,
+                            float density_factor, float* density, float* beta_avg, float* op, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  FieldCall c;
+  if (field_check(M, K, N, R, x, nbr, row, centers, inv_sr, strengths, min_scale, c) != GSR_OK) return GSR_EINVAL;
+  c.density_factor = density_factor;
+  if (M == 0) {  // nothing to launch, no device touched
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (density == nullptr || beta_avg == nullptr || workspace == nullptr)
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (workspace_bytes < field_workspace_bytes(0, K, N)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_field_forward(c, density, beta_avg, op, workspace, (hipStream_t)stream);
+  return last_launch();
+}
+
+int gsr_sugar_field_backward(int M, int K, int N, int R, const float* x, const long long* nbr, const long long* row,
+                             const float* centers, const float* inv_sr, const float* strengths, const float* min_scale,
+                             float density_factor, const float* dL_ddensity, const float* dL_dbeta_avg,
+                             const float* dL_dop, float* dL_dx, float* dL_dcenters, float* dL_dinv_sr,
+                             float* dL_dstrengths, float* dL_dmin_scale, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  FieldCall c;
+  if (field_check(M, K, N, R, x, nbr, row, centers, inv_sr, strengths, min_scale, c) != GSR_OK) return GSR_EINVAL;
+  c.density_factor = density_factor;
+  if (M == 0) {
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (dL_dx == nullptr || workspace == nullptr ||
+      (N > 0 && (dL_dcenters == nullptr || dL_dinv_sr == nullptr || dL_dstrengths == nullptr ||
+                 dL_dmin_scale == nullptr)))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (workspace_bytes < field_workspace_bytes(M, K, N)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  const int e = launch_field_backward(c, dL_ddensity, dL_dbeta_avg, dL_dop, dL_dx, dL_dcenters, dL_dinv_sr,
+                                      dL_dstrengths, dL_dmin_scale, workspace, (hipStream_t)stream);
+  if (e != 0) return fail(GSR_EHIP, "HIP error: %s", hipGetErrorString((hipError_t)e));
+  return last_launch();
+}
+
 // ---- the view-segmented radix sort (tests: every sort of the library runs seg_sort) -----------------
 struct SortWork {
   uint32_t *keys2, *vals2, *counts, *totals;

@@ -229,6 +229,25 @@ int launch_knn_mean_dist(int P, const float* points, float* out, void* workspace
 // the same tree and workspace; dists / idx are (P, K), rows ascending by (squared distance, input index).
 int launch_knn_points(int P, int K, const float* points, float* dists, long long* idx, void* workspace,
                       hipStream_t stream);
+// The SuGaR neighbour density field (include/gsr.h gsr_sugar_field_*) — gsr_field.hip.  M samples, K neighbour slots,
+// N Gaussians, nbr (R, K); row (M,) or null (then R = M).  The forward uses the first field_workspace_bytes(0, K, N)
+// bytes of the workspace only.
+struct FieldCall {
+  int M, K, N, R;
+  const float* x;
+  const long long *nbr, *row;
+  const float *centers, *inv_sr, *strengths, *min_scale;
+  float density_factor;
+};
+size_t field_workspace_bytes(long long M, int K, int N);
+// lanes per Gaussian of the backward's per-Gaussian sums (64 or 16: part of the documented sum order)
+int field_gauss_lanes(long long M, int K, int N);
+void launch_field_forward(const FieldCall& c, float* density, float* beta_avg, float* op, void* workspace,
+                          hipStream_t stream);
+// 0, or the hipError_t of a failed stream operation
+int launch_field_backward(const FieldCall& c, const float* g_density, const float* g_beta, const float* g_op, float* dx,
+                          float* dcenters, float* dinv_sr, float* dstrengths, float* dmin_scale, void* workspace,
+                          hipStream_t stream);
 void launch_gauss_backward(const GaussBackwardArgs& a, ViewGradArgs va, const AccumArgs& b, hipStream_t stream);
 
 }  // namespace gsr

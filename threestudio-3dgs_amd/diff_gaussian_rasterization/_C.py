@@ -103,6 +103,9 @@ SIGNATURES = {
     "gsr_knn_mean_dist": (_i, [_i, _vp, _vp, _vp, _sz, _vp]),
     "gsr_knn_points_workspace_bytes": (_sz, [_i, _i]),
     "gsr_knn_points": (_i, [_i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gsr_sugar_field_workspace_bytes": (_sz, [_i, _i, _i]),
+    "gsr_sugar_field_forward": (_i, [_i, _i, _i, _i] + [_vp] * 7 + [_f] + [_vp] * 4 + [_sz, _vp]),
+    "gsr_sugar_field_backward": (_i, [_i, _i, _i, _i] + [_vp] * 7 + [_f] + [_vp] * 9 + [_sz, _vp]),
     "gsr_set_geom_bytes": (_sz, [_i, _i]),
     "gsr_set_binning_bytes": (_sz, [_i, _i, ctypes.POINTER(_i), _i, _i]),
     "gsr_set_image_bytes": (_sz, [_i, _i, _ip, _i, _i, _i]),
@@ -155,7 +158,7 @@ def host_trace_read(reset: bool = True) -> dict:
     return out
 
 
-ABI_VERSION = 7  # include/gsr.h GSR_ABI_VERSION this binding is written against
+ABI_VERSION = 8  # include/gsr.h GSR_ABI_VERSION this binding is written against
 
 
 def load_library(path: str | None = None):

@@ -1,0 +1,211 @@
+"""The SuGaR regulariser's neighbour density field over the C ABI (include/gsr.h gsr_sugar_field_*, csrc/gsr_field.hip).
+
+The reference evaluates, every training step of system/sugar_static.py:260-285, ``SuGaRRegularizer.get_field_values``
+(utils/sugar_utils.py:278-353) at M = 500 000 samples against K = 16 neighbours each: it gathers (M, K, 3, 3) inverse
+scaled rotations, (M, K, 3) centres and (M, K) strengths, runs a batched matmul over them, keeps all of it for autograd
+and scatters the backward into the Gaussians with ``index_put`` atomics.  Here one fused kernel gathers and reduces,
+and the backward recomputes from the inputs and sums per Gaussian in a fixed order (no atomics: two calls give the
+same bits).
+
+``neighbor_density`` is the fused, differentiable part; ``get_field_values`` composes the M-sized remainder in torch in
+the reference's own order and returns its ``fields`` dict.  For the reference to pick this up, two lines change in
+``SuGaRRegularizer.get_field_values``: its body becomes
+
+    from sugar_field import get_field_values
+    return get_field_values(x, points=gaussian_centers, inv_scaled_rotation=gaussian_inv_scaled_rotation,
+                            strengths=gaussian_strengths, scaling=self.scaling, knn_idx=self.knn_idx,
+                            gaussian_idx=gaussian_idx, closest_gaussians_idx=closest_gaussians_idx,
+                            beta_mode=self.beta_mode, log_beta=getattr(self, "_log_beta", None), ...)
+
+after the three ``if ... is None`` defaults it already has.  GPU only, like ``simple_knn.knn_points``.
+"""
+from __future__ import annotations
+
+import math
+import operator
+
+import torch
+
+from diff_gaussian_rasterization import _C as _gsr
+
+__all__ = ["neighbor_density", "get_field_values", "FIELD_MAX_K"]
+
+FIELD_MAX_K = 32  # include/gsr.h GSR_KNN_MAX_K
+
+
+class _NeighborDensity(torch.autograd.Function):
+    """(x, centers, inv_sr, strengths, min_scale) -> (density, beta_avg, op | None); nbr / row are index tensors."""
+
+    @staticmethod
+    def forward(ctx, x, centers, inv_sr, strengths, min_scale, nbr, row, density_factor, want_op):
+        dev = x.device
+        lib = _gsr.load_library()
+        M, K, N, R = int(x.shape[0]), int(nbr.shape[1]), int(centers.shape[0]), int(nbr.shape[0])
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, centers, inv_sr, strengths, min_scale, nbr, row)
+        ctx.density_factor = density_factor
+        fopt = dict(dtype=torch.float32, device=dev)
+        density = torch.empty((M,), **fopt)
+        beta_avg = torch.empty((M,), **fopt)
+        op = torch.empty((M, K), **fopt) if want_op else None
+        if M > 0:
+            nbytes = int(lib.gsr_sugar_field_workspace_bytes(0, K, N))
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            _gsr._check(lib.gsr_sugar_field_forward(
+                M, K, N, R, _gsr._ptr(x), _gsr._ptr(nbr), _gsr._ptr(row), _gsr._ptr(centers), _gsr._ptr(inv_sr),
+                _gsr._ptr(strengths), _gsr._ptr(min_scale), density_factor, _gsr._ptr(density), _gsr._ptr(beta_avg),
+                _gsr._ptr(op), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
+        if op is None:
+            return density, beta_avg, None
+        return density, beta_avg, op
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_density, g_beta, g_op):
+        x, centers, inv_sr, strengths, min_scale, nbr, row = ctx.saved_tensors
+        dev = x.device
+        M, K, N, R = int(x.shape[0]), int(nbr.shape[1]), int(centers.shape[0]), int(nbr.shape[0])
+        if M == 0 or (g_density is None and g_beta is None and g_op is None):
+            grads = tuple(torch.zeros_like(t) for t in (x, centers, inv_sr, strengths, min_scale))
+            return grads + (None, None, None, None)
+        lib = _gsr.load_library()
+        g_density, g_beta, g_op = (None if g is None else _gsr._f32(g, "upstream gradient", dev)
+                                   for g in (g_density, g_beta, g_op))
+        dx, dc, dA, ds, dms = (torch.empty_like(t) for t in (x, centers, inv_sr, strengths, min_scale))
+        nbytes = int(lib.gsr_sugar_field_workspace_bytes(M, K, N))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        _gsr._check(lib.gsr_sugar_field_backward(
+            M, K, N, R, _gsr._ptr(x), _gsr._ptr(nbr), _gsr._ptr(row), _gsr._ptr(centers), _gsr._ptr(inv_sr),
+            _gsr._ptr(strengths), _gsr._ptr(min_scale), ctx.density_factor, _gsr._ptr(g_density), _gsr._ptr(g_beta),
+            _gsr._ptr(g_op), _gsr._ptr(dx), _gsr._ptr(dc), _gsr._ptr(dA), _gsr._ptr(ds), _gsr._ptr(dms),
+            _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
+        return dx, dc, dA, ds, dms, None, None, None, None
+
+
+def _float_tensor(t, name, shape):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise ValueError(f"{name} must be a float32 tensor")
+    if t.dim() != len(shape) or any(s is not None and int(t.shape[i]) != s for i, s in enumerate(shape)):
+        want = ", ".join("*" if s is None else str(s) for s in shape)
+        raise ValueError(f"{name} must have shape ({want}), got {tuple(t.shape)}")
+    return t
+
+
+def _index_tensor(t, name, dims):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != dims:
+        raise ValueError(f"{name} must be an int64 tensor with {dims} dimension(s)")
+    return t
+
+
+def _neighbour_table(M, knn_idx, gaussian_idx, closest_gaussians_idx):
+    """(nbr (R, K), row (M,) | None) of the one index form given."""
+    table = knn_idx is not None and gaussian_idx is not None
+    if table == (closest_gaussians_idx is not None) or (not table and (knn_idx is not None
+                                                                      or gaussian_idx is not None)):
+        raise ValueError("give either knn_idx with gaussian_idx, or closest_gaussians_idx (one of the two forms)")
+    if table:
+        nbr, row = _index_tensor(knn_idx, "knn_idx", 2), _index_tensor(gaussian_idx, "gaussian_idx", 1)
+        if int(row.shape[0]) != M:
+            raise ValueError(f"gaussian_idx must have one entry per sample ({M}), got {int(row.shape[0])}")
+    else:
+        nbr, row = _index_tensor(closest_gaussians_idx, "closest_gaussians_idx", 2), None
+        if int(nbr.shape[0]) != M:
+            raise ValueError(f"closest_gaussians_idx must have one row per sample ({M}), got {int(nbr.shape[0])}")
+    if not 1 <= int(nbr.shape[1]) <= FIELD_MAX_K:
+        raise ValueError(f"the neighbour table must have 1..{FIELD_MAX_K} columns, got {int(nbr.shape[1])}")
+    return nbr, row
+
+
+def neighbor_density(x, centers, inv_scaled_rotation, strengths, min_scaling, *, knn_idx=None, gaussian_idx=None,
+                     closest_gaussians_idx=None, density_factor=1.0, return_opacities=False):
+    """The neighbour sum of ``get_field_values`` and the ``average`` beta, fused and differentiable.
+
+    x (M, 3) samples; centers (N, 3); inv_scaled_rotation (N, 3, 3) = ``get_covariance(return_full_matrix=True,
+    return_sqrt=True, inverse_scales=True)``; strengths (N,) or (N, 1); min_scaling (N,) = ``scaling.min(-1)[0]``; all
+    float32 on the GPU.  Neighbours: either ``knn_idx`` (N, K) with ``gaussian_idx`` (M,) — sample m uses the row
+    ``knn_idx[gaussian_idx[m]]``, read in the kernel — or ``closest_gaussians_idx`` (M, K); int64, 1 <= K <= 32.
+
+    Returns ``(density, beta_avg, opacities)``: density (M,) = sum_k op[m, k] (raw, before any normalisation),
+    beta_avg (M,) = mean_k min_scaling[j], and op (M, K) = density_factor strengths_j exp(-clamp(|A_j^T (x - c_j)|^2,
+    0, 1e8) / 2) when ``return_opacities`` (else None).  A neighbour index outside [0, N) (``knn_points``' -1 padding)
+    contributes nothing; a ``gaussian_idx`` outside the table gives zeros.  Gradients flow to all five float inputs,
+    bitwise reproducible; no double backward.
+    """
+    x = _float_tensor(x, "x", (None, 3))
+    M = int(x.shape[0])
+    centers = _float_tensor(centers, "centers", (None, 3))
+    N = int(centers.shape[0])
+    inv_sr = _float_tensor(inv_scaled_rotation, "inv_scaled_rotation", (N, 3, 3))
+    if isinstance(strengths, torch.Tensor) and strengths.dim() == 2:
+        strengths = _float_tensor(strengths, "strengths", (N, 1)).reshape(N)
+    strengths = _float_tensor(strengths, "strengths", (N,))
+    min_scaling = _float_tensor(min_scaling, "min_scaling", (N,))
+    nbr, row = _neighbour_table(M, knn_idx, gaussian_idx, closest_gaussians_idx)
+    try:
+        density_factor = float(density_factor)
+    except (TypeError, ValueError):
+        raise ValueError("density_factor must be a number") from None
+    dev = x.device
+    _gsr._require_gpu(dev)
+    for name, t in (("centers", centers), ("inv_scaled_rotation", inv_sr), ("strengths", strengths),
+                    ("min_scaling", min_scaling), ("neighbour indices", nbr), ("gaussian_idx", row)):
+        if t is not None and t.device != dev:
+            raise _gsr.GSRError(f"{name} is on {t.device}, expected {dev}")
+    return _NeighborDensity.apply(x.contiguous(), centers.contiguous(), inv_sr.contiguous(), strengths.contiguous(),
+                                  min_scaling.contiguous(), nbr.contiguous(),
+                                  None if row is None else row.contiguous(), density_factor,
+                                  bool(operator.truth(return_opacities)))
+
+
+def get_field_values(x, *, points, inv_scaled_rotation, strengths, scaling, knn_idx=None, gaussian_idx=None,
+                     closest_gaussians_idx=None, beta_mode="average", log_beta=None, return_sdf=True,
+                     density_threshold=1., density_factor=1., return_sdf_grad=False, opacity_min_clamp=1e-16,
+                     return_closest_gaussian_opacities=False, return_beta=False):
+    """``SuGaRRegularizer.get_field_values`` (utils/sugar_utils.py:278-353) with ``get_beta`` (:400-471) as a function of
+    the regulariser's tensors: points (N, 3), inv_scaled_rotation (N, 3, 3), strengths (N, 1) or (N,), scaling (N, 3).
+    Returns the reference's ``fields`` dict: 'density' always, 'closest_gaussian_opacities', 'beta', 'sdf' on request.
+    The fused kernel supplies density, opacities and the ``average`` beta; the rest is the reference's own torch
+    arithmetic in its order.  ``return_sdf_grad`` is not built."""
+    if return_sdf_grad:
+        raise NotImplementedError("get_field_values: return_sdf_grad is not supported")
+    if beta_mode not in ("learnable", "average", "weighted_average"):
+        raise ValueError("Unknown beta_mode.")
+    need_beta = return_sdf or return_beta
+    if need_beta and beta_mode == "learnable" and not isinstance(log_beta, torch.Tensor):
+        raise ValueError("beta_mode='learnable' needs log_beta")
+    scaling = _float_tensor(scaling, "scaling", (None, 3))
+    min_scaling = scaling.min(dim=-1)[0]
+    weighted = need_beta and beta_mode == "weighted_average"
+    density, beta_avg, opacities = neighbor_density(
+        x, points, inv_scaled_rotation, strengths, min_scaling, knn_idx=knn_idx, gaussian_idx=gaussian_idx,
+        closest_gaussians_idx=closest_gaussians_idx, density_factor=density_factor,
+        return_opacities=return_closest_gaussian_opacities or weighted)
+    fields = {"density": density}
+    # normalize density bigger or equal than 1 (by its detached self + 1e-12), on a copy as the reference does
+    densities = density.clone()
+    density_mask = densities >= 1.
+    densities[density_mask] = densities[density_mask] / (densities[density_mask].detach() + 1e-12)
+    if return_closest_gaussian_opacities:
+        fields["closest_gaussian_opacities"] = opacities
+    if need_beta:
+        if beta_mode == "learnable":
+            beta = torch.exp(log_beta).expand(len(x))
+        elif beta_mode == "average":
+            beta = beta_avg
+        else:
+            idx = closest_gaussians_idx if closest_gaussians_idx is not None else knn_idx[gaussian_idx]
+            inside = (idx >= 0) & (idx < min_scaling.shape[0])  # padded slots carry weight 0 and scale 0
+            neighbor_min_scaling = min_scaling[idx.clamp(0, max(int(min_scaling.shape[0]) - 1, 0))] * inside
+            opacities_sum = opacities.sum(dim=-1, keepdim=True)
+            weights = opacities / opacities_sum.clamp(min=opacity_min_clamp)
+            beta = (neighbor_min_scaling * weights).sum(dim=-1)
+            with torch.no_grad():
+                # all opacities 0: far from every Gaussian, beta must not be 0 -> the largest min scale at hand
+                beta[opacities_sum[..., 0] == 0.] = neighbor_min_scaling.max().detach()
+        clamped_densities = densities.clamp(min=opacity_min_clamp)
+    if return_beta:
+        fields["beta"] = beta
+    if return_sdf:
+        fields["sdf"] = beta * (torch.sqrt(-2. * torch.log(clamped_densities))
+                                - math.sqrt(-2. * math.log(min(density_threshold, 1.))))
+    return fields
