@@ -69,6 +69,9 @@ const char* gsr_version(void);
  *      _chunks entry points of revisions 2-5 are gone.
  *   8  gsr_sugar_field_workspace_bytes / gsr_sugar_field_forward / gsr_sugar_field_backward (the SuGaR regulariser's
  *      neighbour density field and its deterministic backward).
+ *      Added under 8 (additive: no existing call changes, binders find the new calls by symbol):
+ *      gsr_sugar_normal_workspace_bytes / gsr_sugar_normal_forward / gsr_sugar_normal_backward (the regulariser's
+ *      neighbour-normal loss).
  */
 #define GSR_ABI_VERSION 8
 int gsr_abi_version(void);
@@ -477,6 +480,63 @@ int gsr_sugar_field_backward(int M, int K, int N, int R, const float* x, const l
                              const float* dL_dop, float* dL_dx, float* dL_dcenters, float* dL_dinv_sr,
                              float* dL_dstrengths, float* dL_dmin_scale, void* workspace, size_t workspace_bytes,
                              void* stream);
+
+/*
+ * The neighbour-normal loss of the SuGaR regulariser ("sdf better normal loss"): replaces the (M,K,3) gathers, the
+ * sign flip, the weight normalisation and the weighted normal sum of coarse_density_regulation
+ * (utils/sugar_utils.py:725-757) and the index_put scatter of their autograd backward.  M samples, K neighbour slots
+ * (1 <= K <= GSR_KNN_MAX_K), N Gaussians, M (K + 1) < 2^31.  All float arrays fp32:
+ *   x (M,3) sample points;  gaussian_idx (M,) int64, the Gaussian i each sample was drawn in;  nbr (R,K) int64;
+ *   centers (N,3);  normals (N,3), need not be unit length;  min_scale (N,) = scaling.min(-1);
+ *   op (M,K), the closest_gaussian_opacities of gsr_sugar_field_forward for the same samples and table.
+ * With nbr_per_sample = 0, sample m reads the table row nbr[gaussian_idx[m]] (the reference's knn_idx, R = N, never
+ * gathered into an (M,K) copy); with nbr_per_sample != 0, R must equal M and sample m reads nbr[m].
+ * For slot k with j = nbr[..][k] and i = gaussian_idx[m]:
+ *   s_k = sign(n_j . n_i)  (sign(0) = 0);   a_k = |(x_m - c_j) . (s_k n_j)|
+ *   w_k = op[m,k] a_k / max(min_scale_j, 1e-6)^2;   W = sum_k w_k;   Wc = max(W, 1e-6);   wh_k = w_k / Wc
+ *   r = n_i - sum_k wh_k s_k n_j;   loss[m] = r . r
+ * s, a, op, min_scale and W are constants of the loss (detached in the reference, whose
+ * sdf_better_normal_gradient_through_normal_only is always on), so only the normals receive a gradient:
+ *   dL/dn_i += 2 dL_dloss[m] r;   dL/dn_j += -2 dL_dloss[m] wh_k s_k r.
+ * Precision: n_j . n_i and (x_m - c_j) . n_j (which cancels: samples lie near their Gaussian's plane) are evaluated
+ * in fp64 per pair and rounded once; everything else is fp32.  r is summed in the equal form
+ *   r = (1 - W / Wc) n_i + sum_k wh_k (n_i - s_k n_j),      1 - W / Wc taken as exactly 0 when W >= 1e-6,
+ * which spares the cancellation of n_i against the sample's own slot (j = i: that term is exactly 0).
+ * Out of range: a slot whose j is outside [0, N) (the -1 padding of gsr_knn_points included) contributes nothing to
+ * the loss or to any gradient, and j is never dereferenced.  A sample whose gaussian_idx[m] is outside [0, N), or
+ * outside [0, R) when it selects the table row, has loss[m] = 0 and no gradient; no row is read for it.
+ * NaN inputs: unspecified values, no out-of-bounds access.
+ * rec (M,4), 16-byte aligned (checked: GSR_EINVAL otherwise), may be NULL in a forward no backward follows: the forward writes (r, Wc) per sample
+ * and the backward reads it (with dL_dloss (M), required); everything else of a pair is recomputed from the inputs,
+ * nothing M x K-sized is kept.  The backward writes dL_dnormals (N,3) in full; rows nothing contributes to are
+ * exactly 0.
+ * Sum orders (no atomics; every result is a pure function of the input, two calls give the same bits):
+ *   over slots (W, and the three components of r): 16 partial sums, partial l = term l (+ term l + 16 when K > 16),
+ *   terms of absent or out-of-range slots 0; the partials are combined pairwise at distances 8, 4, 2, 1
+ *   (t[i] += t[i ^ 8], then ^ 4, ^ 2, ^ 1); then r = fma(1 - W / Wc, n_i, that sum), loss = fma(r2, r2, fma(r1, r1,
+ *   r0 r0)).
+ *   per Gaussian (dL_dnormals): every sample has K + 1 terms, term m (K + 1) + k for slot k < K (coefficient
+ *   -2 dL_dloss[m] wh_k s_k, Gaussian j) and term m (K + 1) + K for the sample's own normal (coefficient
+ *   2 dL_dloss[m], Gaussian i); each term is coefficient x r_m.  A Gaussian's terms are taken in ascending term
+ *   number (a stable radix sort of the terms by Gaussian, csrc/gsr_sort.hip); term number t of the Gaussian goes to
+ *   partial t mod L, each partial adds its terms by fma in that order starting from 0, and the L partials are
+ *   combined pairwise at distances L/2, ..., 2, 1.  L = 64 when M (K + 1) >= 48 N, else 16.
+ * workspace: gsr_sugar_normal_workspace_bytes(M, K, N) bytes of device memory (256-B aligned) for the backward: sort
+ * keys and values double-buffered and one coefficient per term (20 M (K + 1) bytes), the sort's counters
+ * (M (K + 1) / 4 bytes: 256 32-bit words per 4096 terms), one 32-byte record and two 32-bit words per Gaussian: at most 24 M (K + 1) + 80 N + 8192 bytes, nothing
+ * of size 3 M K floats.  The forward needs gsr_sugar_normal_workspace_bytes(0, K, N) (the records) only.  Kernels
+ * run on `stream`; the library allocates nothing.  M = 0 launches nothing and writes nothing (the caller zeroes the
+ * gradient of an empty batch).
+ */
+size_t gsr_sugar_normal_workspace_bytes(int M, int K, int N);
+int gsr_sugar_normal_forward(int M, int K, int N, int R, const float* x, const long long* gaussian_idx,
+                             const long long* nbr, int nbr_per_sample, const float* centers, const float* normals,
+                             const float* min_scale, const float* op, float* loss, float* rec, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int gsr_sugar_normal_backward(int M, int K, int N, int R, const float* x, const long long* gaussian_idx,
+                              const long long* nbr, int nbr_per_sample, const float* centers, const float* normals,
+                              const float* min_scale, const float* op, const float* rec, const float* dL_dloss,
+                              float* dL_dnormals, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * The view-segmented stable LSD radix sort that every sort of this library runs (the depth sort, the tile sort and

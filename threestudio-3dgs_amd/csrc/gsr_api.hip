@@ -554,6 +554,66 @@ int gsr_sugar_field_backward(int M, int K, int N, int R, const float* x, const l
   return last_launch();
 }
 
+// ---- the SuGaR neighbour-normal loss (gsr_normal.hip) ----------------------------------------------
+static int normal_check(int M, int K, int N, int R, const float* x, const long long* gaussian_idx,
+                        const long long* nbr, int nbr_per_sample, const float* centers, const float* normals,
+                        const float* min_scale, const float* op, NormalCall& c) {
+  if (K < 1 || K > GSR_KNN_MAX_K) return fail(GSR_EINVAL, "%s", "K must be in 1..32");
+  if (M < 0 || N < 0 || R < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if ((long long)M * (K + 1) >= (1ll << 31))
+    return fail(GSR_EINVAL, "%s", "M x (K + 1) must stay below 2^31: split the samples");
+  if (nbr_per_sample && R != M) return fail(GSR_EINVAL, "%s", "a per-sample neighbour table has M rows");
+  if (M > 0 && (x == nullptr || gaussian_idx == nullptr || op == nullptr || (R > 0 && nbr == nullptr)))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (N > 0 && (centers == nullptr || normals == nullptr || min_scale == nullptr))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  c = NormalCall{M, K, N, R, x, gaussian_idx, nbr, nbr_per_sample != 0, centers, normals, min_scale, op};
+  return GSR_OK;
+}
+
+size_t gsr_sugar_normal_workspace_bytes(int M, int K, int N) {
+  if (K < 1 || K > GSR_KNN_MAX_K) return 0;
+  return normal_workspace_bytes(M < 0 ? 0 : M, K, N < 0 ? 0 : N);
+}
+
+int gsr_sugar_normal_forward(int M, int K, int N, int R, const float* x, const long long* gaussian_idx,
+                             const long long* nbr, int nbr_per_sample, const float* centers, const float* normals,
+                             const float* min_scale, const float* op, float* loss, float* rec, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  NormalCall c;
+  if (normal_check(M, K, N, R, x, gaussian_idx, nbr, nbr_per_sample, centers, normals, min_scale, op, c) != GSR_OK)
+    return GSR_EINVAL;
+  if (M == 0) {  // nothing to launch, no device touched
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (loss == nullptr || workspace == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (((uintptr_t)rec & 15u) != 0) return fail(GSR_EINVAL, "%s", "rec must be 16-byte aligned");
+  if (workspace_bytes < normal_workspace_bytes(0, K, N)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_normal_forward(c, loss, rec, workspace, (hipStream_t)stream);
+  return last_launch();
+}
+
+int gsr_sugar_normal_backward(int M, int K, int N, int R, const float* x, const long long* gaussian_idx,
+                              const long long* nbr, int nbr_per_sample, const float* centers, const float* normals,
+                              const float* min_scale, const float* op, const float* rec, const float* dL_dloss,
+                              float* dL_dnormals, void* workspace, size_t workspace_bytes, void* stream) {
+  NormalCall c;
+  if (normal_check(M, K, N, R, x, gaussian_idx, nbr, nbr_per_sample, centers, normals, min_scale, op, c) != GSR_OK)
+    return GSR_EINVAL;
+  if (M == 0) {
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (rec == nullptr || dL_dloss == nullptr || workspace == nullptr || (N > 0 && dL_dnormals == nullptr))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (((uintptr_t)rec & 15u) != 0) return fail(GSR_EINVAL, "%s", "rec must be 16-byte aligned");
+  if (workspace_bytes < normal_workspace_bytes(M, K, N)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  const int e = launch_normal_backward(c, rec, dL_dloss, dL_dnormals, workspace, (hipStream_t)stream);
+  if (e != 0) return fail(GSR_EHIP, "HIP error: %s", hipGetErrorString((hipError_t)e));
+  return last_launch();
+}
+
 // ---- the view-segmented radix sort (tests: every sort of the library runs seg_sort) -----------------
 struct SortWork {
   uint32_t *keys2, *vals2, *counts, *totals;

@@ -248,6 +248,23 @@ void launch_field_forward(const FieldCall& c, float* density, float* beta_avg, f
 int launch_field_backward(const FieldCall& c, const float* g_density, const float* g_beta, const float* g_op, float* dx,
                           float* dcenters, float* dinv_sr, float* dstrengths, float* dmin_scale, void* workspace,
                           hipStream_t stream);
+// The SuGaR neighbour-normal loss (include/gsr.h gsr_sugar_normal_*) — gsr_normal.hip.  own (M,) is each sample's
+// Gaussian; nbr (R, K) is read at row m (per_sample, R = M) or at row own[m].  The forward uses the first
+// normal_workspace_bytes(0, K, N) bytes of the workspace only; rec is the forward's (M, 4) record (r, Wc).
+struct NormalCall {
+  int M, K, N, R;
+  const float* x;
+  const long long *own, *nbr;
+  int per_sample;
+  const float *centers, *normals, *min_scale, *op;
+};
+size_t normal_workspace_bytes(long long M, int K, int N);
+// lanes per Gaussian of the backward's per-Gaussian sums (64 or 16: part of the documented sum order)
+int normal_gauss_lanes(long long M, int K, int N);
+void launch_normal_forward(const NormalCall& c, float* loss, float* rec, void* workspace, hipStream_t stream);
+// 0, or the hipError_t of a failed stream operation
+int launch_normal_backward(const NormalCall& c, const float* rec, const float* g_loss, float* dnormals,
+                           void* workspace, hipStream_t stream);
 void launch_gauss_backward(const GaussBackwardArgs& a, ViewGradArgs va, const AccumArgs& b, hipStream_t stream);
 
 }  // namespace gsr

@@ -18,6 +18,12 @@ the reference's own order and returns its ``fields`` dict.  For the reference to
                             beta_mode=self.beta_mode, log_beta=getattr(self, "_log_beta", None), ...)
 
 after the three ``if ... is None`` defaults it already has.  GPU only, like ``simple_knn.knn_points``.
+
+``neighbor_normal_loss`` (include/gsr.h gsr_sugar_normal_*, csrc/gsr_normal.hip) is the other M x K half of the
+regulariser step, the "sdf better normal loss" of ``coarse_density_regulation`` (utils/sugar_utils.py:725-757), fused
+the same way; ``smallest_axis``, ``sample_points_in_gaussians`` and ``coarse_density_regulation`` restate the N- and
+M-sized remainder of that step in torch, so that the body of the reference's ``coarse_density_regulation`` below its
+parameter block becomes one call.
 """
 from __future__ import annotations
 
@@ -28,7 +34,8 @@ import torch
 
 from diff_gaussian_rasterization import _C as _gsr
 
-__all__ = ["neighbor_density", "get_field_values", "FIELD_MAX_K"]
+__all__ = ["neighbor_density", "get_field_values", "neighbor_normal_loss", "smallest_axis",
+           "sample_points_in_gaussians", "coarse_density_regulation", "FIELD_MAX_K"]
 
 FIELD_MAX_K = 32  # include/gsr.h GSR_KNN_MAX_K
 
@@ -209,3 +216,191 @@ def get_field_values(x, *, points, inv_scaled_rotation, strengths, scaling, knn_
         fields["sdf"] = beta * (torch.sqrt(-2. * torch.log(clamped_densities))
                                 - math.sqrt(-2. * math.log(min(density_threshold, 1.))))
     return fields
+
+
+class _NeighborNormalLoss(torch.autograd.Function):
+    """(x, centers, normals, min_scale, op) -> loss (M,); own / nbr are index tensors.  Only normals gets a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, centers, normals, min_scale, op, own, nbr, per_sample):
+        dev = x.device
+        lib = _gsr.load_library()
+        M, K, N, R = int(x.shape[0]), int(nbr.shape[1]), int(centers.shape[0]), int(nbr.shape[0])
+        fopt = dict(dtype=torch.float32, device=dev)
+        loss = torch.empty((M,), **fopt)
+        rec = torch.empty((M, 4), **fopt) if ctx.needs_input_grad[2] else None  # (r, Wc): all the backward keeps
+        if M > 0:
+            nbytes = int(lib.gsr_sugar_normal_workspace_bytes(0, K, N))
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            _gsr._check(lib.gsr_sugar_normal_forward(
+                M, K, N, R, _gsr._ptr(x), _gsr._ptr(own), _gsr._ptr(nbr), int(per_sample), _gsr._ptr(centers),
+                _gsr._ptr(normals), _gsr._ptr(min_scale), _gsr._ptr(op), _gsr._ptr(loss), _gsr._ptr(rec),
+                _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
+        ctx.save_for_backward(x, centers, normals, min_scale, op, own, nbr, rec)
+        ctx.per_sample = per_sample
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        x, centers, normals, min_scale, op, own, nbr, rec = ctx.saved_tensors
+        dev = x.device
+        M, K, N, R = int(x.shape[0]), int(nbr.shape[1]), int(centers.shape[0]), int(nbr.shape[0])
+        if not ctx.needs_input_grad[2]:
+            return (None,) * 8
+        if M == 0 or N == 0:
+            return (None, None, torch.zeros_like(normals)) + (None,) * 5
+        lib = _gsr.load_library()
+        g_loss = _gsr._f32(g_loss, "upstream gradient", dev)
+        dnormals = torch.empty_like(normals)
+        nbytes = int(lib.gsr_sugar_normal_workspace_bytes(M, K, N))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        _gsr._check(lib.gsr_sugar_normal_backward(
+            M, K, N, R, _gsr._ptr(x), _gsr._ptr(own), _gsr._ptr(nbr), int(ctx.per_sample), _gsr._ptr(centers),
+            _gsr._ptr(normals), _gsr._ptr(min_scale), _gsr._ptr(op), _gsr._ptr(rec), _gsr._ptr(g_loss),
+            _gsr._ptr(dnormals), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
+        return (None, None, dnormals) + (None,) * 5
+
+
+def neighbor_normal_loss(x, centers, normals, min_scaling, opacities, *, gaussian_idx, knn_idx=None,
+                         closest_gaussians_idx=None, gradient_through_normal_only=True):
+    """The "sdf better normal loss" of ``coarse_density_regulation`` (utils/sugar_utils.py:725-757) per sample, fused.
+
+    x (M, 3) samples; centers (N, 3); normals (N, 3) = ``get_normals()``, not necessarily unit; min_scaling (N,) =
+    ``scaling.min(-1)[0]``; opacities (M, K) = the ``closest_gaussian_opacities`` of ``get_field_values`` for the same
+    samples; all float32 on the GPU.  gaussian_idx (M,) int64 is the Gaussian i each sample was drawn in.  Neighbours:
+    either ``knn_idx`` (N, K), sample m using the row ``knn_idx[gaussian_idx[m]]`` read in the kernel, or
+    ``closest_gaussians_idx`` (M, K); int64, 1 <= K <= 32.
+
+    Returns loss_normal (M,) = |n_i - sum_k wh_k s_k n_j|^2 with s_k = sign(n_j . n_i), wh_k = w_k / max(sum_k w_k,
+    1e-6) and w_k = op[m, k] |(x_m - c_j) . n_j| / max(min_scaling_j, 1e-6)^2 (zero weight where s_k = 0).  As in the
+    reference, whose ``sdf_better_normal_gradient_through_normal_only`` is always on, the signs and weights are
+    constants and the gradient flows to ``normals`` only; ``gradient_through_normal_only=False`` is not built.  A
+    neighbour index outside [0, N) contributes nothing; a ``gaussian_idx`` outside [0, N) gives 0 and no gradient.
+    Bitwise reproducible, forward and backward; no double backward.
+    """
+    if not gradient_through_normal_only:
+        raise NotImplementedError("neighbor_normal_loss: gradient_through_normal_only=False is not supported")
+    x = _float_tensor(x, "x", (None, 3))
+    M = int(x.shape[0])
+    centers = _float_tensor(centers, "centers", (None, 3))
+    N = int(centers.shape[0])
+    normals = _float_tensor(normals, "normals", (N, 3))
+    min_scaling = _float_tensor(min_scaling, "min_scaling", (N,))
+    own = _index_tensor(gaussian_idx, "gaussian_idx", 1)
+    if int(own.shape[0]) != M:
+        raise ValueError(f"gaussian_idx must have one entry per sample ({M}), got {int(own.shape[0])}")
+    if (knn_idx is None) == (closest_gaussians_idx is None):
+        raise ValueError("give either knn_idx or closest_gaussians_idx (one of the two forms)")
+    nbr, _ = _neighbour_table(M, knn_idx, None if knn_idx is None else own, closest_gaussians_idx)
+    opacities = _float_tensor(opacities, "opacities", (M, int(nbr.shape[1])))
+    dev = x.device
+    _gsr._require_gpu(dev)
+    for name, t in (("centers", centers), ("normals", normals), ("min_scaling", min_scaling),
+                    ("opacities", opacities), ("neighbour indices", nbr), ("gaussian_idx", own)):
+        if t.device != dev:
+            raise _gsr.GSRError(f"{name} is on {t.device}, expected {dev}")
+    return _NeighborNormalLoss.apply(x.contiguous(), centers.contiguous(), normals.contiguous(),
+                                     min_scaling.contiguous(), opacities.contiguous(), own.contiguous(),
+                                     nbr.contiguous(), knn_idx is None)
+
+
+def _quaternion_to_matrix(q):
+    """Rotation matrices (..., 3, 3) of quaternions (w, x, y, z), normalised here."""
+    w, x, y, z = torch.nn.functional.normalize(q, dim=-1).unbind(-1)
+    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                        2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                        2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)],
+                       -1).reshape(q.shape[:-1] + (3, 3))
+
+
+def _quaternion_multiply(a, b):
+    aw, ax, ay, az = a.unbind(-1)
+    bw, bx, by, bz = b.unbind(-1)
+    return torch.stack([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                        aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw], -1)
+
+
+def _quaternion_apply(q, p):
+    """q (0, p) q^-1 for unit q: the rotation of the points p by the quaternions q."""
+    pq = torch.cat([torch.zeros_like(p[..., :1]), p], -1)
+    inv = q * q.new_tensor([1., -1., -1., -1.])
+    return _quaternion_multiply(_quaternion_multiply(q, pq), inv)[..., 1:]
+
+
+def smallest_axis(quaternions, scaling):
+    """``get_smallest_axis`` (utils/sugar_utils.py:355-372), the normals of ``get_normals()`` for Gaussians not bound
+    to a mesh: the column of each rotation matrix at the argmin of its scales, (N, 3).  quaternions (N, 4) are
+    (w, x, y, z) and are normalised here; scaling (N, 3)."""
+    quaternions = _float_tensor(quaternions, "quaternions", (None, 4))
+    scaling = _float_tensor(scaling, "scaling", (int(quaternions.shape[0]), 3))
+    idx = scaling.min(dim=-1)[1][..., None, None].expand(-1, 3, -1)
+    return _quaternion_to_matrix(quaternions).gather(2, idx).squeeze(dim=2)
+
+
+def sample_points_in_gaussians(points, quaternions, scaling, num_samples, sampling_scale_factor=1., *, strengths=None,
+                               mask=None, probabilities_proportional_to_opacity=False,
+                               probabilities_proportional_to_volume=True, generator=None):
+    """``sample_points_in_gaussians`` (utils/sugar_utils.py:183-230): ``(random_points, random_indices)``.
+
+    Faithful to the reference, including that ``torch.multinomial`` is fed the *cumulative* probabilities
+    ``areas.cumsum() / areas.sum()`` as its weights (:214-218), not the probabilities: Gaussian number n of the
+    (masked) list is drawn with a weight proportional to the summed area of Gaussians 0..n, so even the "uniform"
+    setting (neither proportional flag) favours high indices linearly.  quaternions are normalised here;
+    ``generator`` seeds both the draw of the indices and the Gaussian noise (None: the default generator)."""
+    points = _float_tensor(points, "points", (None, 3))
+    n = int(points.shape[0])
+    quaternions = _float_tensor(quaternions, "quaternions", (n, 4))
+    all_scaling = _float_tensor(scaling, "scaling", (n, 3))
+    scaling = all_scaling if mask is None else all_scaling[mask]
+    if probabilities_proportional_to_volume:
+        areas = scaling[..., 0] * scaling[..., 1] * scaling[..., 2]
+    else:
+        areas = torch.ones_like(scaling[..., 0])
+    if probabilities_proportional_to_opacity:
+        if strengths is None:
+            raise ValueError("probabilities_proportional_to_opacity needs strengths")
+        areas = areas * (strengths.view(-1) if mask is None else strengths[mask].view(-1))
+    areas = areas.abs()
+    cum_probs = areas.cumsum(dim=-1) / areas.sum(dim=-1, keepdim=True)
+    random_indices = torch.multinomial(cum_probs, num_samples=num_samples, replacement=True, generator=generator)
+    if mask is not None:
+        random_indices = torch.arange(n, device=points.device)[mask][random_indices]
+    centers = points[random_indices]
+    noise = torch.randn(centers.shape, dtype=centers.dtype, device=centers.device, generator=generator)
+    q = torch.nn.functional.normalize(quaternions, dim=-1)[random_indices]
+    random_points = centers + _quaternion_apply(q, sampling_scale_factor * all_scaling[random_indices] * noise)
+    return random_points, random_indices
+
+
+def coarse_density_regulation(points, quaternions, scaling, strengths, knn_idx, *, n_samples,
+                              use_sdf_better_normal_loss, beta_mode="average", log_beta=None, generator=None):
+    """The regulation losses of ``SuGaRRegularizer.coarse_density_regulation`` (utils/sugar_utils.py:683-759) as a
+    function of the regulariser's tensors: points (N, 3), quaternions (N, 4) (w, x, y, z), scaling (N, 3) and
+    strengths (N, 1) or (N,) as activated by the Gaussian model, knn_idx (N, K).  Returns the reference's
+    ``{"density_regulation", "normal_regulation"}`` with its constants (density_factor 1, density_threshold 1,
+    sampling_scale_factor 1.5, sampling not proportional to volume or opacity).  The two M x K parts are the fused
+    ``neighbor_density`` and ``neighbor_normal_loss``; the rest is the reference's torch arithmetic in its order.
+    ``normal_regulation`` is 0 when ``use_sdf_better_normal_loss`` is off, as is everything for an empty cloud."""
+    loss = {"density_regulation": 0, "normal_regulation": 0}
+    if int(points.shape[0]) == 0:
+        return loss
+    sdf_samples, sdf_gaussian_idx = sample_points_in_gaussians(
+        points, quaternions, scaling, n_samples, 1.5, probabilities_proportional_to_volume=False, generator=generator)
+    rotation = _quaternion_to_matrix(quaternions)
+    inv_scaled_rotation = rotation * (1. / scaling.clamp(min=1e-8))[:, None]
+    fields = get_field_values(
+        sdf_samples, points=points, inv_scaled_rotation=inv_scaled_rotation, strengths=strengths, scaling=scaling,
+        knn_idx=knn_idx, gaussian_idx=sdf_gaussian_idx, beta_mode=beta_mode, log_beta=log_beta, return_sdf=False,
+        density_threshold=1., density_factor=1., return_closest_gaussian_opacities=use_sdf_better_normal_loss,
+        return_beta=True)
+    gaussians_normals = smallest_axis(quaternions, scaling)
+    samples_gaussian_normals = gaussians_normals[sdf_gaussian_idx]
+    sdf_estimation = ((sdf_samples - points[sdf_gaussian_idx]) * samples_gaussian_normals).sum(dim=-1)
+    target_densities = torch.exp(-0.5 * sdf_estimation.pow(2) / fields["beta"].pow(2))
+    loss["density_regulation"] = loss["density_regulation"] + (fields["density"] - target_densities).abs().mean()
+    if use_sdf_better_normal_loss:
+        loss["normal_regulation"] = loss["normal_regulation"] + neighbor_normal_loss(
+            sdf_samples.detach(), points.detach(), gaussians_normals, scaling.min(dim=-1)[0].detach(),
+            fields["closest_gaussian_opacities"].detach(), gaussian_idx=sdf_gaussian_idx, knn_idx=knn_idx).mean()
+    return loss
