@@ -539,6 +539,58 @@ int gsr_sugar_normal_backward(int M, int K, int N, int R, const float* x, const 
                               float* dL_dnormals, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The geometry of SuGaR Gaussians bound to a mesh: replaces SuGaRModel.points, .scaling, .quaternions and
+ * .get_gs_normals (geometry/sugar.py:449-536), i.e. the (F,3,3) vertex gather, the pytorch3d face normals, the three
+ * normalisations, the two cross products, the (N,3,3) concatenation, matrix_to_quaternion and the index_put scatter of
+ * their autograd backward.  V vertices, F faces, G Gaussians per face (1 <= G <= GSR_MESH_MAX_G), N = F G (passed,
+ * and checked: GSR_EINVAL otherwise), N < 2^31:
+ *   verts (V,3) fp32;  faces (F,3) int32;  bary (G,3) fp32 in HOST memory (read during the call);
+ *   complex_numbers (N,2) fp32, the in-plane rotation;  log_scales (N,2) fp32;  thickness, the normal-axis scale.
+ * Gaussian f G + g belongs to face f.  With p0, p1, p2 = verts[faces[f]] and normalize(v, eps) = v / max(|v|, eps):
+ *   c = (p1 - p0) x (p2 - p0);   n = normalize(c, 1e-6) (pytorch3d's face normal);   R0 = normalize(n, 1e-12)
+ *   b1 = normalize(p0 - p1, 1e-12);   b2 = normalize(R0 x b1, 1e-12)
+ *   z = normalize(complex_numbers, 1e-12);   R1 = z0 b1 + z1 b2;   R2 = -z1 b1 + z0 b2
+ *   q = matrix_to_quaternion([R0 | R1 | R2]) (columns): with a_i = sqrt_pos of 1+m00+m11+m22, 1+m00-m11-m22,
+ *   1-m00+m11-m22, 1-m00-m11+m22 (sqrt_pos(x) = sqrt(x) for x > 0, else 0 with zero gradient), the candidate rows
+ *   (a0^2, m21-m12, m02-m20, m10-m01), (m21-m12, a1^2, m10+m01, m02+m20), (m02-m20, m10+m01, a2^2, m12+m21),
+ *   (m10-m01, m20+m02, m21+m12, a3^2), each divided by 2 max(a_i, 0.1); the row of the largest a_i is taken, the
+ *   lowest index on ties; order (w, x, y, z); no sign standardisation.
+ *   xyz = sum_k bary[g][k] p_k;   scaling = (thickness, exp(log_scales));   rotation = normalize(q, 1e-12);
+ *   normals = R0 (the same for the G Gaussians of a face).
+ * Outputs xyz (N,3), scaling (N,3), rotation (N,4), normals (N,3), all required.  rotation and dL_drotation must be
+ * 16-byte aligned, complex_numbers, log_scales and their gradients 8-byte aligned (checked: GSR_EINVAL otherwise).
+ * Precision: the per-face frame, the per-Gaussian part and the gradient arithmetic are all evaluated in fp64 from the
+ * fp32 inputs; every output and gradient is rounded to fp32 once, except dL_dverts: its per-corner terms are rounded
+ * to fp32 once (the corner rows), added in fp64 and the sum rounded once.
+ * Backward: the exact derivative of the composition above (the clamps pass the gradient where |v| >= eps and make the
+ * quotient linear below; the candidate row is a constant choice).  dL_dxyz (N,3), dL_dscaling (N,3), dL_drotation
+ * (N,4), dL_dnormals (N,3): any may be NULL (zero).  Writes in full dL_dverts (V,3), dL_dcomplex (N,2) and
+ * dL_dlog_scales (N,2); a vertex no face uses gets exactly 0.  The frame is recomputed from the inputs: the forward
+ * keeps nothing.  corner_order (3F,) int32 and vert_offsets (V+1,) int32 are the vertex incidence: the corners
+ * (numbered 3 f + c) of vertex v are corner_order[vert_offsets[v] .. vert_offsets[v+1]).
+ * Out of range: a face with an entry outside [0, V) has all four outputs, its Gaussians' gradients and its corner
+ * rows 0, and the entry is never dereferenced.  A corner_order entry outside [0, 3F) is skipped; offsets are clamped
+ * to [0, 3F].  NaN inputs: unspecified values, no out-of-bounds access.
+ * Sum orders (no atomics; every result is a pure function of the input, two calls give the same bits):
+ *   per face (the gradients to R0, b1, b2 and the bary-weighted dL_dxyz to each corner): its Gaussians in ascending
+ *   g, each partial starting from 0; the frame's own terms are added after the last Gaussian.
+ *   per vertex (dL_dverts): its corner rows in the order of corner_order, sequentially, starting from 0.
+ * workspace (backward only): gsr_sugar_mesh_workspace_bytes(F, V) bytes of device memory (256-B aligned): the corner
+ * rows, 36 F bytes (at least 256, also for F = 0).  Kernels run on `stream`; the library allocates nothing.  The
+ * forward is one launch, the backward two.  F = 0 launches nothing and writes nothing (the caller zeroes dL_dverts).
+ */
+#define GSR_MESH_MAX_G 8
+size_t gsr_sugar_mesh_workspace_bytes(int F, int V);
+int gsr_sugar_mesh_forward(int V, int F, int G, int N, const float* verts, const int* faces, const float* bary,
+                           const float* complex_numbers, const float* log_scales, float thickness, float* xyz,
+                           float* scaling, float* rotation, float* normals, void* stream);
+int gsr_sugar_mesh_backward(int V, int F, int G, int N, const float* verts, const int* faces, const float* bary,
+                            const float* complex_numbers, const float* log_scales, const int* corner_order,
+                            const int* vert_offsets, const float* dL_dxyz, const float* dL_dscaling,
+                            const float* dL_drotation, const float* dL_dnormals, float* dL_dverts, float* dL_dcomplex,
+                            float* dL_dlog_scales, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The view-segmented stable LSD radix sort that every sort of this library runs (the depth sort, the tile sort and
  * distCUDA2's Morton sort: csrc/gsr_sort.hip; it replaces the reference extension's cub::DeviceRadixSort::SortPairs
  * calls of one view at a time).  Exposed for tests: V (1..64) segments of n[v] (key, value) pairs laid

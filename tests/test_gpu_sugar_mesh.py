@@ -1,0 +1,272 @@
+"""sugar_mesh.bound_gaussians (include/gsr.h gsr_sugar_mesh_*, csrc/gsr_mesh.hip) on the GPU against the fp64 torch
+restatement of the same formulas (tests/sugar_mesh_reference.py), differentiated by autograd on the CPU.
+
+Bar.  Per tensor (the four outputs, the three gradients): max |gpu - ref64| / max |ref64| <= 2 x the same figure of the
+fp32 torch composition on the same inputs (the restatement in float32 on the CPU, the "fp32 null", computed here):
+the kernel may not be less exact than twice what it replaces.  The factor 2 is there because the null is itself a few
+ulps of one rounding sample.  Where the reference tensor is all zero the result must be exactly zero.  Before
+comparing, each quaternion row's sign is aligned with the sign of its dot product with the reference row (the kernel
+and the reference may take different candidate rows of matrix_to_quaternion where two tie), and that row's upstream
+gradient is multiplied by the same sign, on the null's side too.  The thickness column of `scaling` and the gradients
+of outputs without an upstream gradient are exact.  Each check prints its figures.
+Measured on the CPU (icosphere(3), G = 6), the null: 1e-7 to 1.7e-7 for all outputs and gradients.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+import gsr_synthetic as gs  # noqa: E402
+import sugar_mesh_reference as ref  # noqa: E402
+
+THICKNESS = 3.5e-6
+
+
+def _rel(a, b):
+    scale = float(b.double().abs().max()) if b.numel() else 0.0
+    return float((a.double() - b.double()).abs().max()) / scale if scale > 0 else 0.0
+
+
+class _Case:
+    """A mesh with random per-Gaussian parameters and upstream gradients; the reference and the null computed once."""
+
+    def __init__(self, verts, faces, G, seed=0, bary=None):
+        from sugar_mesh import MeshBinding
+
+        self.verts = torch.as_tensor(np.asarray(verts), dtype=torch.float32)
+        self.faces = torch.as_tensor(np.asarray(faces), dtype=torch.int64)
+        if bary is None:
+            self.binding = MeshBinding.from_reference_count(self.faces, len(self.verts), G)
+        else:
+            self.binding = MeshBinding(self.faces, len(self.verts), bary)
+        gen = torch.Generator().manual_seed(seed)
+        N = self.binding.n_gaussians
+        self.cplx = torch.randn(N, 2, generator=gen)
+        self.log_scales = torch.randn(N, 2, generator=gen) * 0.3 - 4
+        self.ups = {k: torch.randn(N, 4 if k == "rotation" else 3, generator=gen) for k in ref.OUTPUTS}
+        self._refs = {}
+
+    def evaluate(self, dtype, ups, sign=None):
+        return ref.evaluate(dtype, self.verts, self.faces, self.binding.bary, self.cplx, self.log_scales, THICKNESS,
+                            ups, sign=sign)
+
+    def reference(self, which):
+        """(fp64 reference without alignment, fp32 null, its row signs, the reference aligned to the null) for the
+        upstream gradients named in `which`."""
+        if which not in self._refs:
+            ups = {k: self.ups[k] for k in which}
+            r0 = self.evaluate(torch.float64, ups)
+            null = self.evaluate(torch.float32, ups)
+            sn = ref.row_sign(null["rotation"], r0["rotation"])
+            rn = r0 if bool((sn > 0).all()) else self.evaluate(torch.float64, ups, sign=sn)
+            self._refs[which] = (r0, null, sn, rn)
+        return self._refs[which]
+
+    def gpu(self, which=ref.OUTPUTS, binding=None):
+        from sugar_mesh import bound_gaussians
+
+        leaves = [t.cuda().requires_grad_() for t in (self.verts, self.cplx, self.log_scales)]
+        out = bound_gaussians(*leaves, (binding or self.binding).to("cuda"), THICKNESS)
+        loss = sum((o * self.ups[k].cuda()).sum() for k, o in zip(ref.OUTPUTS, out) if k in which)
+        grads = torch.autograd.grad(loss, leaves)
+        got = {k: v.detach().cpu() for k, v in zip(ref.OUTPUTS, out)}
+        got.update({k: g.cpu() for k, g in zip(ref.GRADS, grads)})
+        return got
+
+    def check(self, got, which=ref.OUTPUTS, tag=""):
+        which = tuple(which)
+        r0, null, sn, rn = self.reference(which)
+        s = ref.row_sign(got["rotation"], r0["rotation"])
+        r = r0
+        if not bool((s > 0).all()):
+            # the GPU result was computed with the plain upstream gradient: a flipped row's reference gradient is
+            # that of -q, i.e. the reference with that row's upstream gradient negated
+            r = self.evaluate(torch.float64, {k: self.ups[k] for k in which}, sign=s)
+        N = self.binding.n_gaussians
+        assert torch.equal(got["scaling"][:, 0], torch.full((N,), THICKNESS, dtype=torch.float32)), tag
+        for k in ref.OUTPUTS + ref.GRADS:
+            assert got[k].dtype == torch.float32 and got[k].shape == r[k].shape, (tag, k, got[k].shape)
+            a = got[k] * s[:, None].float() if k == "rotation" else got[k]
+            n = null[k] * sn[:, None].float() if k == "rotation" else null[k]
+            err, bar = _rel(a, r[k]), 2 * _rel(n, rn[k])
+            print(f"{tag} {k}: gpu {err:.3g}  fp32 null {bar / 2:.3g}  flipped rows {int((s < 0).sum())}")
+            if not r[k].any():
+                assert not got[k].any(), (tag, k)  # nothing contributes: exactly zero
+            else:
+                assert torch.isfinite(got[k]).all() and err <= bar, (tag, k, err, bar)
+
+
+def _icosphere_case(subdiv, G):
+    v, f = gs.icosphere(subdiv)
+    return _Case(v, f, G, seed=10 * subdiv + G)
+
+
+@functools.lru_cache(maxsize=None)
+def _ico3():
+    return _icosphere_case(3, 6)
+
+
+@functools.lru_cache(maxsize=None)
+def _ico3_gpu():
+    return _ico3().gpu()
+
+
+def _fan(n=200):
+    """n faces around vertex 0 (a closed, slightly crumpled fan) and one extra vertex no face uses."""
+    ang = np.arange(n) * (2 * np.pi / n)
+    ring = np.stack([np.cos(ang), np.sin(ang), 0.1 * np.sin(7 * ang)], 1)
+    verts = np.concatenate([[[0.0, 0.0, 0.3]], ring, [[2.0, 2.0, 2.0]]])
+    faces = np.stack([np.zeros(n, np.int64), 1 + np.arange(n), 1 + (np.arange(n) + 1) % n], 1)
+    return verts, faces
+
+
+@pytest.mark.gpu
+def test_one_face_one_gaussian():
+    case = _Case([[0.1, 0.2, 0.3], [0.9, 0.1, 0.2], [0.3, 0.8, 0.5]], [[0, 1, 2]], 1, seed=1)
+    assert case.binding.n_gaussians == 1
+    case.check(case.gpu(), tag="F=1 G=1")
+
+
+@pytest.mark.gpu
+def test_two_triangles_sharing_an_edge():
+    case = _Case([[0., 0., 0.], [1., 0., 0.1], [0., 1., 0.2], [1.1, 0.9, -0.3]], [[0, 1, 2], [2, 1, 3]], 3, seed=2)
+    case.check(case.gpu(), tag="two triangles G=3")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("G", [1, 3, 4, 6])
+def test_icosphere0(G):
+    """12 vertices of valence 5, every barycentric set of the reference."""
+    case = _icosphere_case(0, G)
+    assert case.binding.n_verts == 12 and case.binding.n_faces == 20
+    case.check(case.gpu(), tag=f"icosphere(0) G={G}")
+
+
+@pytest.mark.gpu
+def test_icosphere3_all_outputs():
+    """V = 642, F = 1280, N = 7680: 30 blocks of Gaussians, 5 of faces, 3 of vertices, none a whole number of faces;
+    the four candidate rows of matrix_to_quaternion are each taken by about a quarter of the Gaussians."""
+    case = _ico3()
+    assert (case.binding.n_verts, case.binding.n_faces, case.binding.n_gaussians) == (642, 1280, 7680)
+    counts = torch.bincount(case.reference(ref.OUTPUTS)[0]["branch"], minlength=4)
+    assert int(counts.min()) > 1500, counts.tolist()
+    case.check(_ico3_gpu(), tag="icosphere(3) G=6")
+
+
+@pytest.mark.gpu
+def test_custom_barycentric_set_of_eight():
+    """G = 8, the largest, with weights that are not the reference's."""
+    gen = torch.Generator().manual_seed(8)
+    bary = torch.rand(8, 3, generator=gen) + 0.05
+    bary = bary / bary.sum(-1, keepdim=True)
+    v, f = gs.icosphere(1)
+    case = _Case(v, f, 8, seed=18, bary=bary)
+    case.check(case.gpu(), tag="icosphere(1) G=8")
+
+
+@pytest.mark.gpu
+def test_fan_of_200_faces_and_an_unused_vertex():
+    verts, faces = _fan(200)
+    case = _Case(verts, faces, 3, seed=3)
+    assert int(case.binding.vert_offsets[1]) == 200 and int(case.binding.vert_offsets[-1]) == 600
+    got = case.gpu()
+    case.check(got, tag="fan")
+    assert torch.equal(got["verts"][-1], torch.zeros(3))  # the vertex no face uses: exactly 0.0
+    assert not torch.signbit(got["verts"][-1]).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", [("xyz",), ("rotation",)])
+def test_partial_upstream_gradients(which):
+    """Only one output carries a gradient (the others arrive as None): the restatement with the others zeroed."""
+    case = _icosphere_case(1, 6)
+    got = case.gpu(which)
+    case.check(got, which, tag=f"only {which[0]}")
+    assert not got["log_scales"].any()  # scaling has no upstream gradient: exactly zero
+    if which == ("xyz",):
+        assert not got["complex"].any()
+        assert got["verts"].any()
+
+
+@pytest.mark.gpu
+def test_degenerate_face():
+    """A face with two equal corners appended to icosphere(0): everything finite, and nothing else changes."""
+    v, f = gs.icosphere(0)
+    G = 6
+    clean = _Case(v, f, G, seed=4)
+    full = _Case(v, np.concatenate([f, [[0, 0, 5]]]), G, seed=4)
+    n = clean.binding.n_gaussians
+    for name in ("cplx", "log_scales"):  # the same parameters for the shared Gaussians
+        getattr(full, name)[:n] = getattr(clean, name)
+    for k in ref.OUTPUTS:
+        full.ups[k][:n] = clean.ups[k]
+    a, b = clean.gpu(), full.gpu()
+    for k in ref.OUTPUTS + ref.GRADS:
+        assert torch.isfinite(b[k]).all(), k
+    for k in ref.OUTPUTS + ("complex", "log_scales"):
+        assert torch.equal(a[k], b[k][:n]), k
+    untouched = [i for i in range(12) if i not in (0, 5)]
+    assert torch.equal(a["verts"][untouched], b["verts"][untouched])
+    assert not b["normals"][n:].any()  # no normal: the zero vector
+    assert torch.equal(b["rotation"][n:], torch.tensor([[1., 0., 0., 0.]]).expand(G, 4))
+
+
+@pytest.mark.gpu
+def test_face_entry_out_of_range_is_not_dereferenced():
+    """A binding whose face table was damaged after its check: that face gives zeros, the others are unchanged."""
+    case = _icosphere_case(1, 6)
+    good = case.gpu()
+    bad = case.binding.to("cpu")
+    bad.faces = bad.faces.clone()
+    bad.faces[3, 1] = case.binding.n_verts + 7
+    bad.faces[9, 2] = -1
+    got = case.gpu(binding=bad)
+    hit = torch.zeros(case.binding.n_gaussians, dtype=torch.bool)
+    hit[3 * 6:4 * 6] = True
+    hit[9 * 6:10 * 6] = True
+    for k in ref.OUTPUTS + ("complex", "log_scales"):
+        assert not got[k][hit].any(), k
+        assert torch.equal(got[k][~hit], good[k][~hit]), k
+    assert torch.isfinite(got["verts"]).all()
+    far = torch.ones(case.binding.n_verts, dtype=torch.bool)
+    far[case.faces[[3, 9]].reshape(-1)] = False
+    assert torch.equal(got["verts"][far], good["verts"][far])
+
+
+@pytest.mark.gpu
+def test_bitwise_repeatable():
+    a, b = _ico3_gpu(), _ico3().gpu()
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+
+
+@pytest.mark.gpu
+def test_outputs_feed_the_sugar_normal_render():
+    """icosphere(3)'s bound Gaussians through rasterize_views in the SuGaR normal renderer's form (the face normals
+    as the second colour set), one 64 x 64 view: it renders, and the gradient reaches the vertices."""
+    from diff_gaussian_rasterization.batched import rasterize_views
+    from gsr_testutil import make_camera
+    from sugar_mesh import bound_gaussians, initial_log_scales
+    from test_gpu_configs import _settings
+
+    case = _ico3()
+    dev = "cuda"
+    binding = case.binding.to(dev)
+    verts = case.verts.to(dev).requires_grad_()
+    cplx = case.cplx.to(dev).requires_grad_()
+    log_scales = initial_log_scales(verts.detach(), binding).requires_grad_()
+    xyz, scaling, rotation, normals = bound_gaussians(verts, cplx, log_scales, binding, THICKNESS)
+    P = binding.n_gaussians
+    gen = torch.Generator().manual_seed(5)
+    colors = torch.rand(P, 3, generator=gen).to(dev)
+    opacities = (torch.rand(P, 1, generator=gen) * 0.39 + 0.6).to(dev)
+    m2 = torch.zeros((P, 3), device=dev, requires_grad=True)
+    c, r, d, a, c2 = rasterize_views([_settings(make_camera(64, 64), [0.0, 0.0, 0.0], 0)], xyz, [m2], opacities,
+                                     colors_precomp=colors, scales=scaling, rotations=rotation, colors2=normals)
+    assert c.shape == (1, 3, 64, 64) and c2.shape == (1, 3, 64, 64) and float(a.detach().max()) > 0.5
+    u = [torch.randn(t.shape, generator=gen).to(dev) for t in (c, d, a, c2)]
+    ((c * u[0]).sum() + (d * u[1]).sum() + (a * u[2]).sum() + (c2 * u[3]).sum()).backward()
+    for name, t in (("verts", verts), ("complex", cplx), ("log_scales", log_scales)):
+        assert t.grad is not None and torch.isfinite(t.grad).all() and t.grad.any(), name

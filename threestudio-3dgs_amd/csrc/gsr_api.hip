@@ -614,6 +614,62 @@ int gsr_sugar_normal_backward(int M, int K, int N, int R, const float* x, const 
   return last_launch();
 }
 
+// ---- the geometry of mesh-bound SuGaR Gaussians (gsr_mesh.hip) -------------------------------------
+static int mesh_check(int V, int F, int G, int N, const float* verts, const int* faces, const float* bary,
+                      const float* complex_numbers, const float* log_scales, MeshCall& c) {
+  if (G < 1 || G > GSR_MESH_MAX_G) return fail(GSR_EINVAL, "%s", "G must be in 1..8");
+  if (V < 0 || F < 0 || N < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if ((long long)F * G != (long long)N) return fail(GSR_EINVAL, "%s", "N must equal F x G");
+  if (bary == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (F > 0 && (faces == nullptr || complex_numbers == nullptr || log_scales == nullptr || (V > 0 && verts == nullptr)))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if ((((uintptr_t)complex_numbers | (uintptr_t)log_scales) & 7u) != 0)
+    return fail(GSR_EINVAL, "%s", "complex_numbers and log_scales must be 8-byte aligned");
+  c = MeshCall{V, F, G, verts, faces, complex_numbers, log_scales};
+  return GSR_OK;
+}
+
+size_t gsr_sugar_mesh_workspace_bytes(int F, int V) { return mesh_workspace_bytes(F < 0 ? 0 : F, V < 0 ? 0 : V); }
+
+int gsr_sugar_mesh_forward(int V, int F, int G, int N, const float* verts, const int* faces, const float* bary,
+                           const float* complex_numbers, const float* log_scales, float thickness, float* xyz,
+                           float* scaling, float* rotation, float* normals, void* stream) {
+  MeshCall c;
+  if (mesh_check(V, F, G, N, verts, faces, bary, complex_numbers, log_scales, c) != GSR_OK) return GSR_EINVAL;
+  if (F == 0) {  // nothing to launch, no device touched
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (xyz == nullptr || scaling == nullptr || rotation == nullptr || normals == nullptr)
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (((uintptr_t)rotation & 15u) != 0) return fail(GSR_EINVAL, "%s", "rotation must be 16-byte aligned");
+  launch_mesh_forward(c, bary, thickness, xyz, scaling, rotation, normals, (hipStream_t)stream);
+  return last_launch();
+}
+
+int gsr_sugar_mesh_backward(int V, int F, int G, int N, const float* verts, const int* faces, const float* bary,
+                            const float* complex_numbers, const float* log_scales, const int* corner_order,
+                            const int* vert_offsets, const float* dL_dxyz, const float* dL_dscaling,
+                            const float* dL_drotation, const float* dL_dnormals, float* dL_dverts, float* dL_dcomplex,
+                            float* dL_dlog_scales, void* workspace, size_t workspace_bytes, void* stream) {
+  MeshCall c;
+  if (mesh_check(V, F, G, N, verts, faces, bary, complex_numbers, log_scales, c) != GSR_OK) return GSR_EINVAL;
+  if (F == 0) {
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (corner_order == nullptr || vert_offsets == nullptr || dL_dcomplex == nullptr || dL_dlog_scales == nullptr ||
+      workspace == nullptr || (V > 0 && dL_dverts == nullptr))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (((uintptr_t)dL_drotation & 15u) != 0) return fail(GSR_EINVAL, "%s", "dL_drotation must be 16-byte aligned");
+  if ((((uintptr_t)dL_dcomplex | (uintptr_t)dL_dlog_scales) & 7u) != 0)
+    return fail(GSR_EINVAL, "%s", "dL_dcomplex and dL_dlog_scales must be 8-byte aligned");
+  if (workspace_bytes < mesh_workspace_bytes(F, V)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_mesh_backward(c, bary, corner_order, vert_offsets, dL_dxyz, dL_dscaling, dL_drotation, dL_dnormals, dL_dverts,
+                       dL_dcomplex, dL_dlog_scales, workspace, (hipStream_t)stream);
+  return last_launch();
+}
+
 // ---- the view-segmented radix sort (tests: every sort of the library runs seg_sort) -----------------
 struct SortWork {
   uint32_t *keys2, *vals2, *counts, *totals;

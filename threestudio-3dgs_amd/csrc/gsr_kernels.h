@@ -265,6 +265,21 @@ void launch_normal_forward(const NormalCall& c, float* loss, float* rec, void* w
 // 0, or the hipError_t of a failed stream operation
 int launch_normal_backward(const NormalCall& c, const float* rec, const float* g_loss, float* dnormals,
                            void* workspace, hipStream_t stream);
+// The geometry of mesh-bound SuGaR Gaussians (include/gsr.h gsr_sugar_mesh_*) — gsr_mesh.hip.  V vertices, F faces,
+// G Gaussians per face; cplx and log_scales are (F G, 2).  bary (G, 3) is host memory.  The backward's workspace
+// holds the (3 F, 3) corner rows.
+struct MeshCall {
+  int V, F, G;
+  const float* verts;
+  const int* faces;
+  const float *cplx, *log_scales;
+};
+size_t mesh_workspace_bytes(int F, int V);
+void launch_mesh_forward(const MeshCall& c, const float* bary, float thickness, float* xyz, float* scaling,
+                         float* rotation, float* normals, hipStream_t stream);
+void launch_mesh_backward(const MeshCall& c, const float* bary, const int* corner_order, const int* vert_offsets,
+                          const float* g_xyz, const float* g_scaling, const float* g_rotation, const float* g_normals,
+                          float* dverts, float* dcplx, float* dlog_scales, void* workspace, hipStream_t stream);
 void launch_gauss_backward(const GaussBackwardArgs& a, ViewGradArgs va, const AccumArgs& b, hipStream_t stream);
 
 }  // namespace gsr
