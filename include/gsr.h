@@ -71,7 +71,12 @@ const char* gsr_version(void);
  *      neighbour density field and its deterministic backward).
  *      Added under 8 (additive: no existing call changes, binders find the new calls by symbol):
  *      gsr_sugar_normal_workspace_bytes / gsr_sugar_normal_forward / gsr_sugar_normal_backward (the regulariser's
- *      neighbour-normal loss).
+ *      neighbour-normal loss);
+ *      gsr_sugar_mesh_workspace_bytes / gsr_sugar_mesh_forward / gsr_sugar_mesh_backward (the geometry of mesh-bound
+ *      SuGaR Gaussians);
+ *      gsr_sugar_skin_workspace_bytes / gsr_sugar_skin_forward / gsr_sugar_skin_backward and
+ *      gsr_sugar_timed_workspace_bytes / gsr_sugar_timed_forward / gsr_sugar_timed_backward (dynamic SuGaR: the
+ *      deformation-graph skinning of the vertices and the Gaussians of the deformed mesh, for all frames of a batch).
  */
 #define GSR_ABI_VERSION 8
 int gsr_abi_version(void);
@@ -589,6 +594,96 @@ int gsr_sugar_mesh_backward(int V, int F, int G, int N, const float* verts, cons
                             const int* vert_offsets, const float* dL_dxyz, const float* dL_dscaling,
                             const float* dL_drotation, const float* dL_dnormals, float* dL_dverts, float* dL_dcomplex,
                             float* dL_dlog_scales, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Dynamic SuGaR, the time-batched geometry of geometry/dynamic_sugar.py, in two calls for all T frames of a batch.
+ * Quaternions marked xyzw are pypose's (x, y, z, w); `rotation` and `rotation0` are this library's (w, x, y, z).
+ * (x) is the Hamilton product, conj negates the vector part, (a, 0) is the pure quaternion of a vector.
+ *   Log(q), q = (v, w) != 0 of any norm: s v with s = 2 atan(|v| / w) / |v| (the plain arctangent of the quotient:
+ *     Log(q) = Log(-q) = Log(c q), |s v| <= pi; pi / |v| at w = 0); for |v|^2 < 1e-8 w^2 the series
+ *     s = 2 / w - 2 |v|^2 / (3 w^3), so that Log and its derivative (2 / w I to v, 0 to w) are exact at the identity.
+ *   Exp(phi) = (k phi, c), theta = |phi|, k = sin(theta / 2) / theta, c = cos(theta / 2); for theta^2 < 1e-8 the series
+ *     k = 1/2 - theta^2 / 48, c = 1 - theta^2 / 8.
+ *   R(q) p = p + 2 v x (v x p + w p) for a unit q.
+ *
+ * gsr_sugar_skin_*: the deformation-graph skinning of the mesh vertices (_get_timed_vertex_attributes_from_dg,
+ * dynamic_sugar.py:505-575).  T frames, V vertices, P nodes, K nodes per vertex (1 <= K <= GSR_SKIN_MAX_K);
+ * T V, T P and V K < 2^31.
+ *   verts (V,3);  node_xyz (P,3);  node_trans (T,P,3);  node_rots (T,P,4) xyzw, non-zero, any norm, 16-byte aligned;
+ *   node_scales (T,P,3) or NULL;  nbr (V,K) int32, the nodes of a vertex;  w (V,K) fp32, their weights.
+ * With q^ = q / |q| per (t, node) and p = verts[v], the sums over the K nodes of v in ascending k, from 0:
+ *   GSR_SKIN_DQS:  d = 1/2 (trans, 0) (x) q^;   S_r = sum w_k q^_k;   S_d = sum w_k d_k;   m = |S_r|;
+ *                  r = S_r / m;   e = S_d / m;   vert_xyz = R(r) p + 2 vec(e (x) conj(r))   (no antipodal sign fix)
+ *   GSR_SKIN_LBS:  vert_xyz = sum w_k (R(q^_k) (p - node_xyz_k) + node_xyz_k + trans_k)
+ *   both:          vert_rot = Exp(sum w_k Log(q_k)) (xyzw, unit, w >= 0);   vert_scale = sum w_k node_scales_k
+ * Outputs vert_xyz (T,V,3), vert_rot (T,V,4) 16-byte aligned, vert_scale (T,V,3) (required iff node_scales is given).
+ * Backward: the exact derivative.  dL_dxyz (T,V,3), dL_drot (T,V,4), dL_dscale (T,V,3): any may be NULL (zero).
+ * Writes in full dL_dverts (V,3), dL_dnode_trans (T,P,3), dL_dnode_rots (T,P,4) (through the normalisation) and, iff
+ * node_scales is given, dL_dnode_scales (T,P,3); a node no vertex uses gets exactly 0.  item_order (V K,) int32 and
+ * node_offsets (P+1,) int32 are the node incidence: the items (numbered v K + k) of node j are
+ * item_order[node_offsets[j] .. node_offsets[j+1]).
+ * Out of range: an nbr entry outside [0, P) contributes nothing and is never used as an index; an item_order entry
+ * outside [0, V K) is skipped; offsets are clamped to [0, V K].  A zero node quaternion or S_r = 0: unspecified
+ * values, no out-of-bounds access (as for NaN inputs).
+ * Sum orders (no atomics; two calls give the same bits): per (t, vertex) its K items ascending; dL_dverts over t
+ * ascending; per (t, node) lane l of one 64-lane wave adds the entries l, l + 64, ... of its list in order, from 0,
+ * and the 64 partial sums are added pairwise by a butterfly (lanes 32 apart first, then 16, ... 1).
+ * Precision: fp64 arithmetic from the fp32 inputs; outputs and gradients are rounded to fp32 once; the per-(t, vertex)
+ * adjoint rows that pass between the backward's kernels are fp32 (one rounding each) and are added in fp64.
+ * workspace (forward and backward): gsr_sugar_skin_workspace_bytes(T, V, P) bytes of device memory (256-B aligned):
+ * 88 T P bytes of per-(t, node) records (q^, d, Log q in fp64) and, used by the backward only, 56 T V bytes of rows.
+ * The forward is two launches, the backward four, on `stream`; the library allocates nothing.  T = 0 or V = 0
+ * launches nothing and writes nothing (the caller zeroes the gradients).
+ *
+ * gsr_sugar_timed_*: the Gaussians of the deformed mesh (get_timed_gs_attributes, fuse_rotations and
+ * get_timed_gs_normals, dynamic_sugar.py:329-346, 618-688).  F faces, G Gaussians per face (1 <= G <=
+ * GSR_MESH_MAX_G), N = F G (passed and checked); T N and T V < 2^31.
+ *   vert_xyz (T,V,3);  vert_rot (T,V,4) xyzw, non-zero;  rotation0 (N,4) wxyz, the static rotation;  faces (F,3)
+ *   int32;  bary (G,3) fp32 in HOST memory;  vert_scale (T,V,3) and log_scales (N,2): both or neither;  thickness.
+ * For Gaussian n = f G + g, with i_c = faces[f][c] and b = bary[g]:
+ *   xyz[t,n] = sum_c b_c vert_xyz[t,i_c];   phi = sum_c b_c Log(vert_rot[t,i_c]);
+ *   rotation[t,n] = normalize(Exp(phi) (x) q0, 1e-12) stored wxyz, q0 = rotation0[n] read as xyzw;
+ *   normals[t,n] = R0 of gsr_sugar_mesh_forward for the deformed face (the zero vector for a degenerate face);
+ *   scaling[t,n] = (thickness, exp(log_scales[n][0] + s_1), exp(log_scales[n][1] + s_2)), s = sum_c b_c
+ *   vert_scale[t,i_c] (s_0 is discarded: its gradient is exactly 0).
+ * Outputs xyz (T,N,3), rotation (T,N,4), normals (T,N,3), scaling (T,N,3) (required iff vert_scale is given).
+ * vert_rot, rotation0, rotation and their gradients must be 16-byte aligned, log_scales and its gradient 8-byte.
+ * Backward: dL_dxyz, dL_drotation, dL_dnormals, dL_dscaling: any may be NULL (zero).  Writes in full dL_dvert_xyz
+ * (T,V,3), dL_dvert_rot (T,V,4), dL_drotation0 (N,4) and, iff vert_scale is given, dL_dvert_scale (T,V,3) and
+ * dL_dlog_scales (N,2); a vertex no face uses gets exactly 0.  corner_order and vert_offsets as for
+ * gsr_sugar_mesh_backward.  Out of range: a face with an entry outside [0, V) has zero outputs, gradients and corner
+ * rows, and the entry is never dereferenced; a corner_order entry outside [0, 3F) is skipped, offsets are clamped.
+ * Sum orders: per (t, face) its Gaussians in ascending g, the normal's terms last; per (t, vertex) its corner rows in
+ * the order of corner_order; dL_drotation0 and dL_dlog_scales over t ascending; all from 0.
+ * workspace (backward only): gsr_sugar_timed_workspace_bytes(T, F) bytes: 120 T F bytes of fp32 corner rows.  The
+ * forward is one launch, the backward three.  T = 0 or F = 0 launches nothing and writes nothing.
+ */
+#define GSR_SKIN_MAX_K 32
+#define GSR_SKIN_DQS 0
+#define GSR_SKIN_LBS 1
+size_t gsr_sugar_skin_workspace_bytes(int T, int V, int P);
+int gsr_sugar_skin_forward(int T, int V, int P, int K, int method, const float* verts, const float* node_xyz,
+                           const float* node_trans, const float* node_rots, const float* node_scales, const int* nbr,
+                           const float* w, float* vert_xyz, float* vert_rot, float* vert_scale, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int gsr_sugar_skin_backward(int T, int V, int P, int K, int method, const float* verts, const float* node_xyz,
+                            const float* node_trans, const float* node_rots, const float* node_scales, const int* nbr,
+                            const float* w, const int* item_order, const int* node_offsets, const float* dL_dxyz,
+                            const float* dL_drot, const float* dL_dscale, float* dL_dverts, float* dL_dnode_trans,
+                            float* dL_dnode_rots, float* dL_dnode_scales, void* workspace, size_t workspace_bytes,
+                            void* stream);
+size_t gsr_sugar_timed_workspace_bytes(int T, int F);
+int gsr_sugar_timed_forward(int T, int V, int F, int G, int N, const float* vert_xyz, const float* vert_rot,
+                            const float* rotation0, const int* faces, const float* bary, const float* vert_scale,
+                            const float* log_scales, float thickness, float* xyz, float* rotation, float* normals,
+                            float* scaling, void* stream);
+int gsr_sugar_timed_backward(int T, int V, int F, int G, int N, const float* vert_xyz, const float* vert_rot,
+                             const float* rotation0, const int* faces, const float* bary, const float* vert_scale,
+                             const float* log_scales, float thickness, const int* corner_order,
+                             const int* vert_offsets, const float* dL_dxyz, const float* dL_drotation,
+                             const float* dL_dnormals, const float* dL_dscaling, float* dL_dvert_xyz,
+                             float* dL_dvert_rot, float* dL_drotation0, float* dL_dvert_scale, float* dL_dlog_scales,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * The view-segmented stable LSD radix sort that every sort of this library runs (the depth sort, the tile sort and

@@ -670,6 +670,145 @@ int gsr_sugar_mesh_backward(int V, int F, int G, int N, const float* verts, cons
   return last_launch();
 }
 
+// ---- the time-batched geometry of dynamic SuGaR (gsr_dynamic.hip) ----------------------------------
+static bool below_2_31(long long a, long long b) { return a * b < (1ll << 31); }
+
+static int skin_check(int T, int V, int P, int K, int method, const float* verts, const float* node_xyz,
+                      const float* node_trans, const float* node_rots, const float* node_scales, const int* nbr,
+                      const float* w, SkinCall& c) {
+  if (K < 1 || K > GSR_SKIN_MAX_K) return fail(GSR_EINVAL, "%s", "K must be in 1..32");
+  if (method != GSR_SKIN_DQS && method != GSR_SKIN_LBS)
+    return fail(GSR_EINVAL, "%s", "method must be GSR_SKIN_DQS or GSR_SKIN_LBS");
+  if (T < 0 || V < 0 || P < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if (!below_2_31(T, V) || !below_2_31(T, P) || !below_2_31(V, K))
+    return fail(GSR_EINVAL, "%s", "T x V, T x P and V x K must stay below 2^31");
+  if (T > 0 && V > 0 &&
+      (P == 0 || verts == nullptr || node_xyz == nullptr || node_trans == nullptr || node_rots == nullptr ||
+       nbr == nullptr || w == nullptr))
+    return fail(GSR_EINVAL, "%s", P == 0 ? "vertices without nodes" : "null pointer argument");
+  if (((uintptr_t)node_rots & 15u) != 0) return fail(GSR_EINVAL, "%s", "node_rots must be 16-byte aligned");
+  c = SkinCall{T, V, P, K, method, verts, node_xyz, node_trans, node_rots, node_scales, nbr, w};
+  return GSR_OK;
+}
+
+size_t gsr_sugar_skin_workspace_bytes(int T, int V, int P) {
+  return skin_workspace_bytes(T < 0 ? 0 : T, V < 0 ? 0 : V, P < 0 ? 0 : P);
+}
+
+int gsr_sugar_skin_forward(int T, int V, int P, int K, int method, const float* verts, const float* node_xyz,
+                           const float* node_trans, const float* node_rots, const float* node_scales, const int* nbr,
+                           const float* w, float* vert_xyz, float* vert_rot, float* vert_scale, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  SkinCall c;
+  if (skin_check(T, V, P, K, method, verts, node_xyz, node_trans, node_rots, node_scales, nbr, w, c) != GSR_OK)
+    return GSR_EINVAL;
+  if (T == 0 || V == 0) {  // nothing to launch, no device touched
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (vert_xyz == nullptr || vert_rot == nullptr || workspace == nullptr ||
+      (node_scales != nullptr && vert_scale == nullptr))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (((uintptr_t)vert_rot & 15u) != 0) return fail(GSR_EINVAL, "%s", "vert_rot must be 16-byte aligned");
+  if (workspace_bytes < skin_workspace_bytes(T, V, P)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_skin_forward(c, vert_xyz, vert_rot, vert_scale, workspace, (hipStream_t)stream);
+  return last_launch();
+}
+
+int gsr_sugar_skin_backward(int T, int V, int P, int K, int method, const float* verts, const float* node_xyz,
+                            const float* node_trans, const float* node_rots, const float* node_scales, const int* nbr,
+                            const float* w, const int* item_order, const int* node_offsets, const float* dL_dxyz,
+                            const float* dL_drot, const float* dL_dscale, float* dL_dverts, float* dL_dnode_trans,
+                            float* dL_dnode_rots, float* dL_dnode_scales, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+  SkinCall c;
+  if (skin_check(T, V, P, K, method, verts, node_xyz, node_trans, node_rots, node_scales, nbr, w, c) != GSR_OK)
+    return GSR_EINVAL;
+  if (T == 0 || V == 0) {
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (item_order == nullptr || node_offsets == nullptr || dL_dverts == nullptr || dL_dnode_trans == nullptr ||
+      dL_dnode_rots == nullptr || workspace == nullptr || (node_scales != nullptr && dL_dnode_scales == nullptr))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if ((((uintptr_t)dL_drot | (uintptr_t)dL_dnode_rots) & 15u) != 0)
+    return fail(GSR_EINVAL, "%s", "dL_drot and dL_dnode_rots must be 16-byte aligned");
+  if (workspace_bytes < skin_workspace_bytes(T, V, P)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_skin_backward(c, item_order, node_offsets, dL_dxyz, dL_drot, node_scales != nullptr ? dL_dscale : nullptr,
+                       dL_dverts, dL_dnode_trans, dL_dnode_rots, dL_dnode_scales, workspace, (hipStream_t)stream);
+  return last_launch();
+}
+
+static int timed_check(int T, int V, int F, int G, int N, const float* vert_xyz, const float* vert_rot,
+                       const float* rotation0, const int* faces, const float* bary, const float* vert_scale,
+                       const float* log_scales, float thickness, TimedCall& c) {
+  if (G < 1 || G > GSR_MESH_MAX_G) return fail(GSR_EINVAL, "%s", "G must be in 1..8");
+  if (T < 0 || V < 0 || F < 0 || N < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if ((long long)F * G != (long long)N) return fail(GSR_EINVAL, "%s", "N must equal F x G");
+  if (!below_2_31(T, N) || !below_2_31(T, V)) return fail(GSR_EINVAL, "%s", "T x N and T x V must stay below 2^31");
+  if (bary == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if ((vert_scale == nullptr) != (log_scales == nullptr))
+    return fail(GSR_EINVAL, "%s", "vert_scale and log_scales are given together or not at all");
+  if (T > 0 && F > 0 &&
+      (faces == nullptr || rotation0 == nullptr || (V > 0 && (vert_xyz == nullptr || vert_rot == nullptr))))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if ((((uintptr_t)vert_rot | (uintptr_t)rotation0) & 15u) != 0)
+    return fail(GSR_EINVAL, "%s", "vert_rot and rotation0 must be 16-byte aligned");
+  if (((uintptr_t)log_scales & 7u) != 0) return fail(GSR_EINVAL, "%s", "log_scales must be 8-byte aligned");
+  c = TimedCall{T, V, F, G, vert_xyz, vert_rot, rotation0, vert_scale, log_scales, faces, thickness};
+  return GSR_OK;
+}
+
+size_t gsr_sugar_timed_workspace_bytes(int T, int F) { return timed_workspace_bytes(T < 0 ? 0 : T, F < 0 ? 0 : F); }
+
+int gsr_sugar_timed_forward(int T, int V, int F, int G, int N, const float* vert_xyz, const float* vert_rot,
+                            const float* rotation0, const int* faces, const float* bary, const float* vert_scale,
+                            const float* log_scales, float thickness, float* xyz, float* rotation, float* normals,
+                            float* scaling, void* stream) {
+  TimedCall c;
+  if (timed_check(T, V, F, G, N, vert_xyz, vert_rot, rotation0, faces, bary, vert_scale, log_scales, thickness, c) !=
+      GSR_OK)
+    return GSR_EINVAL;
+  if (T == 0 || F == 0) {  // nothing to launch, no device touched
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (xyz == nullptr || rotation == nullptr || normals == nullptr || (vert_scale != nullptr && scaling == nullptr))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (((uintptr_t)rotation & 15u) != 0) return fail(GSR_EINVAL, "%s", "rotation must be 16-byte aligned");
+  launch_timed_forward(c, bary, xyz, rotation, normals, scaling, (hipStream_t)stream);
+  return last_launch();
+}
+
+int gsr_sugar_timed_backward(int T, int V, int F, int G, int N, const float* vert_xyz, const float* vert_rot,
+                             const float* rotation0, const int* faces, const float* bary, const float* vert_scale,
+                             const float* log_scales, float thickness, const int* corner_order,
+                             const int* vert_offsets, const float* dL_dxyz, const float* dL_drotation,
+                             const float* dL_dnormals, const float* dL_dscaling, float* dL_dvert_xyz,
+                             float* dL_dvert_rot, float* dL_drotation0, float* dL_dvert_scale, float* dL_dlog_scales,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  TimedCall c;
+  if (timed_check(T, V, F, G, N, vert_xyz, vert_rot, rotation0, faces, bary, vert_scale, log_scales, thickness, c) !=
+      GSR_OK)
+    return GSR_EINVAL;
+  if (T == 0 || F == 0) {
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (corner_order == nullptr || vert_offsets == nullptr || dL_drotation0 == nullptr || workspace == nullptr ||
+      (V > 0 && (dL_dvert_xyz == nullptr || dL_dvert_rot == nullptr)) ||
+      (vert_scale != nullptr && (dL_dlog_scales == nullptr || (V > 0 && dL_dvert_scale == nullptr))))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if ((((uintptr_t)dL_drotation | (uintptr_t)dL_dvert_rot | (uintptr_t)dL_drotation0) & 15u) != 0)
+    return fail(GSR_EINVAL, "%s", "dL_drotation, dL_dvert_rot and dL_drotation0 must be 16-byte aligned");
+  if (((uintptr_t)dL_dlog_scales & 7u) != 0) return fail(GSR_EINVAL, "%s", "dL_dlog_scales must be 8-byte aligned");
+  if (workspace_bytes < timed_workspace_bytes(T, F)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_timed_backward(c, bary, corner_order, vert_offsets, dL_dxyz, dL_drotation, dL_dnormals,
+                        vert_scale != nullptr ? dL_dscaling : nullptr, dL_dvert_xyz, dL_dvert_rot, dL_drotation0,
+                        dL_dvert_scale, dL_dlog_scales, workspace, (hipStream_t)stream);
+  return last_launch();
+}
+
 // ---- the view-segmented radix sort (tests: every sort of the library runs seg_sort) -----------------
 struct SortWork {
   uint32_t *keys2, *vals2, *counts, *totals;

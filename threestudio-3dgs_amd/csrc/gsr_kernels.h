@@ -280,6 +280,35 @@ void launch_mesh_forward(const MeshCall& c, const float* bary, float thickness, 
 void launch_mesh_backward(const MeshCall& c, const float* bary, const int* corner_order, const int* vert_offsets,
                           const float* g_xyz, const float* g_scaling, const float* g_rotation, const float* g_normals,
                           float* dverts, float* dcplx, float* dlog_scales, void* workspace, hipStream_t stream);
+// The time-batched geometry of dynamic SuGaR (include/gsr.h gsr_sugar_skin_*, gsr_sugar_timed_*) — gsr_dynamic.hip.
+// Skinning: T frames, V vertices, P nodes, K nodes per vertex; node_scales may be null.  The workspace holds the
+// per-(t, node) records (forward and backward) and, for the backward, the (T V) adjoint rows and dL/dverts terms.
+struct SkinCall {
+  int T, V, P, K, method;  // GSR_SKIN_DQS or GSR_SKIN_LBS
+  const float *verts, *node_xyz, *node_trans, *node_rots, *node_scales;
+  const int* nbr;
+  const float* w;
+};
+size_t skin_workspace_bytes(int T, int V, int P);
+void launch_skin_forward(const SkinCall& c, float* xyz, float* rot, float* scale, void* workspace, hipStream_t stream);
+void launch_skin_backward(const SkinCall& c, const int* item_order, const int* node_offsets, const float* g_xyz,
+                          const float* g_rot, const float* g_scale, float* dverts, float* dtrans, float* drots,
+                          float* dscales, void* workspace, hipStream_t stream);
+// Timed Gaussians: F faces, G Gaussians per face; vert_scale and log_scales are both given or both null.  bary (G, 3)
+// is host memory.  The backward's workspace holds the (T, 3 F, 10) corner rows.
+struct TimedCall {
+  int T, V, F, G;
+  const float *vert_xyz, *vert_rot, *rotation0, *vert_scale, *log_scales;
+  const int* faces;
+  float thickness;
+};
+size_t timed_workspace_bytes(int T, int F);
+void launch_timed_forward(const TimedCall& c, const float* bary, float* xyz, float* rotation, float* normals,
+                          float* scaling, hipStream_t stream);
+void launch_timed_backward(const TimedCall& c, const float* bary, const int* corner_order, const int* vert_offsets,
+                           const float* g_xyz, const float* g_rotation, const float* g_normals,
+                           const float* g_scaling, float* dvert_xyz, float* dvert_rot, float* drotation0,
+                           float* dvert_scale, float* dlog_scales, void* workspace, hipStream_t stream);
 void launch_gauss_backward(const GaussBackwardArgs& a, ViewGradArgs va, const AccumArgs& b, hipStream_t stream);
 
 }  // namespace gsr

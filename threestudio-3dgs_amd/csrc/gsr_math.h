@@ -166,4 +166,136 @@ __device__ __forceinline__ float3 sh_to_rgb(int deg, const float* sh, const floa
   return make_float3(fmaxf(res.x, 0.0f), fmaxf(res.y, 0.0f), fmaxf(res.z, 0.0f));
 }
 
+// ---- fp64 vectors and quaternions of the SuGaR geometry kernels (gsr_mesh.hip, gsr_dynamic.hip) ----
+// (host-callable too: the bodies of gsr_dynamic.hip can be stepped through on the CPU)
+#define GSR_HD __host__ __device__ __forceinline__
+struct D3 {
+  double x, y, z;
+};
+GSR_HD D3 d3(double x, double y, double z) { return D3{x, y, z}; }
+GSR_HD D3 operator+(D3 a, D3 b) { return d3(a.x + b.x, a.y + b.y, a.z + b.z); }
+GSR_HD D3 operator-(D3 a, D3 b) { return d3(a.x - b.x, a.y - b.y, a.z - b.z); }
+GSR_HD D3 operator*(double s, D3 a) { return d3(s * a.x, s * a.y, s * a.z); }
+GSR_HD double dot(D3 a, D3 b) { return fma(a.z, b.z, fma(a.y, b.y, a.x * b.x)); }
+// (no contraction: the cross product of two equal vectors, a degenerate face, is exactly 0)
+GSR_HD D3 cross(D3 a, D3 b) {
+#pragma clang fp contract(off)
+  return d3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
+}
+// v / max(|v|, eps)
+GSR_HD D3 normalize(D3 v, double eps) { return (1.0 / fmax(sqrt(dot(v, v)), eps)) * v; }
+// the gradient to v of u = v / max(|v|, eps), given the gradient g to u
+GSR_HD D3 normalize_grad(D3 g, D3 v, double eps) {
+  const double len = sqrt(dot(v, v));
+  if (!(len >= eps)) return (1.0 / eps) * g;  // the clamp holds: u is linear in v
+  const double inv = 1.0 / len;
+  const D3 u = inv * v;
+  return inv * (g - dot(u, g) * u);
+}
+GSR_HD D3 load3(const float* p) { return d3((double)p[0], (double)p[1], (double)p[2]); }
+GSR_HD void store3(float* p, D3 v) {
+  p[0] = (float)v.x;
+  p[1] = (float)v.y;
+  p[2] = (float)v.z;
+}
+
+// A quaternion, vector part v and scalar w (pypose stores (x, y, z, w), this library's rotations (w, x, y, z)).
+struct Q4 {
+  D3 v;
+  double w;
+};
+GSR_HD Q4 q4(D3 v, double w) { return Q4{v, w}; }
+GSR_HD Q4 operator+(Q4 a, Q4 b) { return q4(a.v + b.v, a.w + b.w); }
+GSR_HD Q4 operator*(double s, Q4 a) { return q4(s * a.v, s * a.w); }
+GSR_HD double dot(Q4 a, Q4 b) { return fma(a.w, b.w, dot(a.v, b.v)); }
+GSR_HD Q4 conj(Q4 a) { return q4(-1.0 * a.v, a.w); }
+// the Hamilton product; its adjoints: the gradient to a is g (x) conj(b), to b conj(a) (x) g
+GSR_HD Q4 qmul(Q4 a, Q4 b) {
+  return q4(a.w * b.v + b.w * a.v + cross(a.v, b.v), a.w * b.w - dot(a.v, b.v));
+}
+GSR_HD Q4 load_xyzw(const float* p) {
+  const float4 q = *(const float4*)p;
+  return q4(d3((double)q.x, (double)q.y, (double)q.z), (double)q.w);
+}
+
+// below these (|v|^2 / w^2 for Log, |phi|^2 for Exp) the series are taken: their first dropped terms are < 1e-17
+#define GSR_LOG_SERIES 1e-8
+#define GSR_EXP_SERIES 1e-8
+#define GSR_PI 3.14159265358979323846
+
+// Log(q) = s v, q != 0 of any norm: s = 2 atan(|v| / w) / |v| (the plain arctangent of the quotient, pi / |v| at
+// w = 0), the series 2 / w - 2 |v|^2 / (3 w^3) as |v| -> 0.  s, and the two coefficients of the adjoint:
+//   dL/dv = s g + a (v . g) v,   dL/dw = b (v . g)
+struct QLog {
+  double s, a, b;
+};
+GSR_HD QLog qlog_coeffs(Q4 q) {
+  const double n2 = dot(q.v, q.v), w2 = q.w * q.w;
+  QLog r;
+  if (n2 < GSR_LOG_SERIES * w2) {
+    const double iw = 1.0 / q.w, iw2 = iw * iw;
+    r.s = 2.0 * iw - (2.0 / 3.0) * n2 * iw2 * iw;
+    r.a = -(4.0 / 3.0) * iw2 * iw;
+    r.b = -2.0 * iw2 + 2.0 * n2 * iw2 * iw2;
+  } else {
+    const double n = sqrt(n2), in2 = 1.0 / n2, id = 1.0 / (w2 + n2);
+    r.s = (q.w == 0.0 ? GSR_PI : 2.0 * atan(n / q.w)) / n;
+    r.a = (2.0 * q.w * id - r.s) * in2;
+    r.b = -2.0 * id;
+  }
+  return r;
+}
+GSR_HD D3 qlog(Q4 q) { return qlog_coeffs(q).s * q.v; }
+GSR_HD Q4 qlog_grad(Q4 q, D3 g) {
+  const QLog c = qlog_coeffs(q);
+  const double vg = dot(q.v, g);
+  return q4(c.s * g + (c.a * vg) * q.v, c.b * vg);
+}
+
+// Exp(phi) = (k phi, c): k = sin(theta / 2) / theta, c = cos(theta / 2), theta = |phi|; the series 1/2 - theta^2 / 48
+// and 1 - theta^2 / 8 as theta -> 0.  The adjoint: dL/dphi = k g.v + (a (phi . g.v) + b g.w) phi.
+struct QExp {
+  double k, c, a, b;
+};
+GSR_HD QExp qexp_coeffs(D3 phi) {
+  const double t2 = dot(phi, phi);
+  QExp r;
+  if (t2 < GSR_EXP_SERIES) {
+    r.k = 0.5 - t2 * (1.0 / 48.0);
+    r.c = 1.0 - t2 * (1.0 / 8.0);
+    r.a = -1.0 / 24.0;
+    r.b = -0.25;
+  } else {
+    const double t = sqrt(t2);
+    r.k = sin(0.5 * t) / t;
+    r.c = cos(0.5 * t);
+    r.a = (0.5 * r.c - r.k) / t2;
+    r.b = -0.5 * r.k;
+  }
+  return r;
+}
+GSR_HD Q4 qexp(D3 phi) {
+  const QExp e = qexp_coeffs(phi);
+  return q4(e.k * phi, e.c);
+}
+GSR_HD D3 qexp_grad(D3 phi, Q4 g) {
+  const QExp e = qexp_coeffs(phi);
+  return e.k * g.v + (e.a * dot(phi, g.v) + e.b * g.w) * phi;
+}
+
+// R(q) p for a unit q, as the polynomial p + 2 v x (v x p + w p) (every q it is given is a normalised one: the
+// adjoint's radial part is removed by the normalisation that follows it).
+GSR_HD D3 qrotate(Q4 q, D3 p) { return p + 2.0 * cross(q.v, cross(q.v, p) + q.w * p); }
+// R(q)^T g: the gradient to p
+GSR_HD D3 qrotate_grad_p(Q4 q, D3 g) { return g + 2.0 * cross(q.v, cross(q.v, g) - q.w * g); }
+// the gradient to q
+GSR_HD Q4 qrotate_grad_q(Q4 q, D3 p, D3 g) {
+  const D3 vp = cross(q.v, p);
+  return q4(2.0 * (cross(vp + q.w * p, g) + cross(p, cross(g, q.v))), 2.0 * dot(vp, g));
+}
+// the gradient to q of q^ = q / |q|, given the gradient g to q^ (len = |q| > 0)
+GSR_HD Q4 qnormalize_grad(Q4 g, Q4 qhat, double len) {
+  return (1.0 / len) * (g + (-dot(g, qhat)) * qhat);
+}
+
 }  // namespace gsr

@@ -26,38 +26,9 @@
 
 #include "../../include/gsr.h"
 #include "gsr_kernels.h"
+#include "gsr_math.h"
 
 namespace gsr {
-
-struct D3 {
-  double x, y, z;
-};
-__device__ __forceinline__ D3 d3(double x, double y, double z) { return D3{x, y, z}; }
-__device__ __forceinline__ D3 operator+(D3 a, D3 b) { return d3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ D3 operator-(D3 a, D3 b) { return d3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ D3 operator*(double s, D3 a) { return d3(s * a.x, s * a.y, s * a.z); }
-__device__ __forceinline__ double dot(D3 a, D3 b) { return fma(a.z, b.z, fma(a.y, b.y, a.x * b.x)); }
-// (no contraction: the cross product of two equal vectors, a degenerate face, is exactly 0)
-__device__ __forceinline__ D3 cross(D3 a, D3 b) {
-#pragma clang fp contract(off)
-  return d3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
-}
-// v / max(|v|, eps)
-__device__ __forceinline__ D3 normalize(D3 v, double eps) { return (1.0 / fmax(sqrt(dot(v, v)), eps)) * v; }
-// the gradient to v of u = v / max(|v|, eps), given the gradient g to u
-__device__ __forceinline__ D3 normalize_grad(D3 g, D3 v, double eps) {
-  const double len = sqrt(dot(v, v));
-  if (!(len >= eps)) return (1.0 / eps) * g;  // the clamp holds: u is linear in v
-  const double inv = 1.0 / len;
-  const D3 u = inv * v;
-  return inv * (g - dot(u, g) * u);
-}
-__device__ __forceinline__ D3 load3(const float* p) { return d3((double)p[0], (double)p[1], (double)p[2]); }
-__device__ __forceinline__ void store3(float* p, D3 v) {
-  p[0] = (float)v.x;
-  p[1] = (float)v.y;
-  p[2] = (float)v.z;
-}
 
 struct MeshFrame {
   D3 p0, p1, p2;

@@ -112,6 +112,12 @@ SIGNATURES = {
     "gsr_sugar_mesh_workspace_bytes": (_sz, [_i, _i]),
     "gsr_sugar_mesh_forward": (_i, [_i, _i, _i, _i] + [_vp] * 5 + [_f] + [_vp] * 4 + [_vp]),
     "gsr_sugar_mesh_backward": (_i, [_i, _i, _i, _i] + [_vp] * 5 + [_vp] * 2 + [_vp] * 4 + [_vp] * 3 + [_vp, _sz, _vp]),
+    "gsr_sugar_skin_workspace_bytes": (_sz, [_i, _i, _i]),
+    "gsr_sugar_skin_forward": (_i, [_i] * 5 + [_vp] * 7 + [_vp] * 3 + [_vp, _sz, _vp]),
+    "gsr_sugar_skin_backward": (_i, [_i] * 5 + [_vp] * 7 + [_vp] * 2 + [_vp] * 3 + [_vp] * 4 + [_vp, _sz, _vp]),
+    "gsr_sugar_timed_workspace_bytes": (_sz, [_i, _i]),
+    "gsr_sugar_timed_forward": (_i, [_i] * 5 + [_vp] * 7 + [_f] + [_vp] * 4 + [_vp]),
+    "gsr_sugar_timed_backward": (_i, [_i] * 5 + [_vp] * 7 + [_f] + [_vp] * 2 + [_vp] * 4 + [_vp] * 5 + [_vp, _sz, _vp]),
     "gsr_set_geom_bytes": (_sz, [_i, _i]),
     "gsr_set_binning_bytes": (_sz, [_i, _i, ctypes.POINTER(_i), _i, _i]),
     "gsr_set_image_bytes": (_sz, [_i, _i, _ip, _i, _i, _i]),
