@@ -76,7 +76,9 @@ const char* gsr_version(void);
  *      SuGaR Gaussians);
  *      gsr_sugar_skin_workspace_bytes / gsr_sugar_skin_forward / gsr_sugar_skin_backward and
  *      gsr_sugar_timed_workspace_bytes / gsr_sugar_timed_forward / gsr_sugar_timed_backward (dynamic SuGaR: the
- *      deformation-graph skinning of the vertices and the Gaussians of the deformed mesh, for all frames of a batch).
+ *      deformation-graph skinning of the vertices and the Gaussians of the deformed mesh, for all frames of a batch);
+ *      gsr_sugar_arap_workspace_bytes / gsr_sugar_arap_forward / gsr_sugar_arap_backward (dynamic SuGaR: the
+ *      as-rigid-as-possible energy of the deformed vertices, for all frames of a batch).
  */
 #define GSR_ABI_VERSION 8
 int gsr_abi_version(void);
@@ -684,6 +686,48 @@ int gsr_sugar_timed_backward(int T, int V, int F, int G, int N, const float* ver
                              const float* dL_dnormals, const float* dL_dscaling, float* dL_dvert_xyz,
                              float* dL_dvert_rot, float* dL_drotation0, float* dL_dvert_scale, float* dL_dlog_scales,
                              void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * gsr_sugar_arap_*: the as-rigid-as-possible energy of the deformed vertices with given per-vertex rotations
+ * (ARAPCoach.compute_arap_energy with vert_rotations, utils/arap_utils.py:148-189, which _compute_arap_energy of
+ * system/sugar_4dgen.py calls once per frame), for all T frames of a batch.  V vertices, E directed one-ring edges;
+ * T V < 2^31.
+ *   verts (V,3): the rest vertices;  offsets (V+1,) int32, nbr (E,) int32, w (E,) fp32: the one-rings in CSR, vertex i
+ *   owning entries offsets[i] .. offsets[i+1]), nbr the neighbour j, w the edge weight w_ij (the caller's: the
+ *   reference's are cotangent weights and may be negative);  vert_xyz (T,V,3): the deformed vertices x';  vert_rot:
+ *   rot_form GSR_ARAP_MATRIX: (T,V,3,3) row-major matrices R;  GSR_ARAP_QUAT: (T,V,4) xyzw quaternions of any norm,
+ *   16-byte aligned, R = I + 2 w [v]x + 2 [v]x^2 (pypose's matrix(): no normalisation).
+ * With p_ij = verts[i] - verts[j] (formed here, exactly), d_ij = x'_i - x'_j and s_ij = d_ij - R_i p_ij at frame t:
+ *   energy[t] = sum_i sum_{j in row i} w_ij |s_ij|^2                                             energy (T,)
+ * Backward, given dL_denergy (T,) = g: writes in full
+ *   dL_dvert_xyz[t,i] = 2 g_t sum_{j in row i} w_ij (2 d_ij - (R_i + R_j) p_ij)                   (T,V,3)
+ *   dL_dvert_rot[t,i] = -2 g_t sum_{j in row i} w_ij s_ij p_ij^T   (T,V,3,3), or its chain to the four quaternion
+ *   components (T,V,4), 16-byte aligned.
+ * The first is the exact derivative when the rows are symmetric (j in row i iff i in row j, w_ij = w_ji), as one-rings
+ * are: then row i holds every term x'_i takes part in, and the backward gathers.  No gradient to verts or w.
+ * A vertex with an empty row gets exactly 0, and so does every row of a frame with g_t = 0.
+ * Out of range: an nbr entry outside [0, V) contributes nothing and is never used as an index; offsets are clamped
+ * to [0, E], a row whose end precedes its start is empty.
+ * Sum orders (no atomics; two calls give the same bits): a row of at most 32 entries is added in ascending entry
+ * order, from 0; of a longer row, lane l of a 64-lane wave adds the entries l, l + 64, ... in order, from 0, and the 64
+ * partial sums are added pairwise by a butterfly (lanes 32 apart first, then 16, ... 1).  The energy: each block of 256
+ * consecutive vertices of a frame adds its lanes' sums by that butterfly per wave and the four wave sums in ascending
+ * order; one wave per frame adds the ceil(V / 256) block sums the same way (lane l: l, l + 64, ...; butterfly).
+ * Precision: fp64 arithmetic from the fp32 inputs; energies and gradients are rounded to fp32 once.  verts = vert_xyz
+ * bitwise with identity rotations gives energy and gradients exactly 0.
+ * workspace (forward only): gsr_sugar_arap_workspace_bytes(T, V) bytes of device memory (256-B aligned): 8 T
+ * ceil(V / 256) bytes of fp64 block sums.  The forward is two launches, the backward one, on `stream`; the library
+ * allocates nothing.  T = 0 or V = 0 launches nothing and writes nothing.
+ */
+#define GSR_ARAP_QUAT 0
+#define GSR_ARAP_MATRIX 1
+size_t gsr_sugar_arap_workspace_bytes(int T, int V);
+int gsr_sugar_arap_forward(int T, int V, int E, int rot_form, const float* verts, const int* offsets, const int* nbr,
+                           const float* w, const float* vert_xyz, const float* vert_rot, float* energy,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int gsr_sugar_arap_backward(int T, int V, int E, int rot_form, const float* verts, const int* offsets, const int* nbr,
+                            const float* w, const float* vert_xyz, const float* vert_rot, const float* dL_denergy,
+                            float* dL_dvert_xyz, float* dL_dvert_rot, void* stream);
 
 /*
  * The view-segmented stable LSD radix sort that every sort of this library runs (the depth sort, the tile sort and

@@ -809,6 +809,57 @@ int gsr_sugar_timed_backward(int T, int V, int F, int G, int N, const float* ver
   return last_launch();
 }
 
+// ---- the ARAP energy of the deformed mesh (gsr_arap.hip) --------------------------------------------
+static int arap_check(int T, int V, int E, int rot_form, const float* verts, const int* offsets, const int* nbr,
+                      const float* w, const float* vert_xyz, const float* vert_rot, ArapCall& c) {
+  if (rot_form != GSR_ARAP_QUAT && rot_form != GSR_ARAP_MATRIX)
+    return fail(GSR_EINVAL, "%s", "rot_form must be GSR_ARAP_QUAT or GSR_ARAP_MATRIX");
+  if (T < 0 || V < 0 || E < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if (!below_2_31(T, V)) return fail(GSR_EINVAL, "%s", "T x V must stay below 2^31");
+  if (T > 0 && V > 0 &&
+      (verts == nullptr || offsets == nullptr || vert_xyz == nullptr || vert_rot == nullptr ||
+       (E > 0 && (nbr == nullptr || w == nullptr))))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (rot_form == GSR_ARAP_QUAT && ((uintptr_t)vert_rot & 15u) != 0)
+    return fail(GSR_EINVAL, "%s", "vert_rot must be 16-byte aligned");
+  c = ArapCall{T, V, E, rot_form, verts, w, vert_xyz, vert_rot, offsets, nbr};
+  return GSR_OK;
+}
+
+size_t gsr_sugar_arap_workspace_bytes(int T, int V) { return arap_workspace_bytes(T < 0 ? 0 : T, V < 0 ? 0 : V); }
+
+int gsr_sugar_arap_forward(int T, int V, int E, int rot_form, const float* verts, const int* offsets, const int* nbr,
+                           const float* w, const float* vert_xyz, const float* vert_rot, float* energy,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  ArapCall c;
+  if (arap_check(T, V, E, rot_form, verts, offsets, nbr, w, vert_xyz, vert_rot, c) != GSR_OK) return GSR_EINVAL;
+  if (T == 0 || V == 0) {  // nothing to launch, no device touched
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (energy == nullptr || workspace == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (workspace_bytes < arap_workspace_bytes(T, V)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_arap_forward(c, energy, workspace, (hipStream_t)stream);
+  return last_launch();
+}
+
+int gsr_sugar_arap_backward(int T, int V, int E, int rot_form, const float* verts, const int* offsets, const int* nbr,
+                            const float* w, const float* vert_xyz, const float* vert_rot, const float* dL_denergy,
+                            float* dL_dvert_xyz, float* dL_dvert_rot, void* stream) {
+  ArapCall c;
+  if (arap_check(T, V, E, rot_form, verts, offsets, nbr, w, vert_xyz, vert_rot, c) != GSR_OK) return GSR_EINVAL;
+  if (T == 0 || V == 0) {
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (dL_denergy == nullptr || dL_dvert_xyz == nullptr || dL_dvert_rot == nullptr)
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (rot_form == GSR_ARAP_QUAT && ((uintptr_t)dL_dvert_rot & 15u) != 0)
+    return fail(GSR_EINVAL, "%s", "dL_dvert_rot must be 16-byte aligned");
+  launch_arap_backward(c, dL_denergy, dL_dvert_xyz, dL_dvert_rot, (hipStream_t)stream);
+  return last_launch();
+}
+
 // ---- the view-segmented radix sort (tests: every sort of the library runs seg_sort) -----------------
 struct SortWork {
   uint32_t *keys2, *vals2, *counts, *totals;

@@ -309,6 +309,17 @@ void launch_timed_backward(const TimedCall& c, const float* bary, const int* cor
                            const float* g_xyz, const float* g_rotation, const float* g_normals,
                            const float* g_scaling, float* dvert_xyz, float* dvert_rot, float* drotation0,
                            float* dvert_scale, float* dlog_scales, void* workspace, hipStream_t stream);
+// The as-rigid-as-possible energy of the deformed mesh (include/gsr.h gsr_sugar_arap_*) — gsr_arap.hip.  T frames, V
+// vertices, E directed one-ring edges in CSR (offsets (V+1,), nbr and w (E,)); verts: the rest vertices; vert_rot
+// (T, V, 4) xyzw or (T, V, 3, 3) by rot_form.  The forward's workspace holds one fp64 partial sum per block.
+struct ArapCall {
+  int T, V, E, rot_form;  // GSR_ARAP_QUAT or GSR_ARAP_MATRIX
+  const float *verts, *w, *vert_xyz, *vert_rot;
+  const int *offsets, *nbr;
+};
+size_t arap_workspace_bytes(int T, int V);
+void launch_arap_forward(const ArapCall& c, float* energy, void* workspace, hipStream_t stream);
+void launch_arap_backward(const ArapCall& c, const float* g_energy, float* dxyz, float* drot, hipStream_t stream);
 void launch_gauss_backward(const GaussBackwardArgs& a, ViewGradArgs va, const AccumArgs& b, hipStream_t stream);
 
 }  // namespace gsr

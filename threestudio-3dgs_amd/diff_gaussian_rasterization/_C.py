@@ -118,6 +118,9 @@ SIGNATURES = {
     "gsr_sugar_timed_workspace_bytes": (_sz, [_i, _i]),
     "gsr_sugar_timed_forward": (_i, [_i] * 5 + [_vp] * 7 + [_f] + [_vp] * 4 + [_vp]),
     "gsr_sugar_timed_backward": (_i, [_i] * 5 + [_vp] * 7 + [_f] + [_vp] * 2 + [_vp] * 4 + [_vp] * 5 + [_vp, _sz, _vp]),
+    "gsr_sugar_arap_workspace_bytes": (_sz, [_i, _i]),
+    "gsr_sugar_arap_forward": (_i, [_i] * 4 + [_vp] * 6 + [_vp] + [_vp, _sz, _vp]),
+    "gsr_sugar_arap_backward": (_i, [_i] * 4 + [_vp] * 6 + [_vp] + [_vp] * 2 + [_vp]),
     "gsr_set_geom_bytes": (_sz, [_i, _i]),
     "gsr_set_binning_bytes": (_sz, [_i, _i, ctypes.POINTER(_i), _i, _i]),
     "gsr_set_image_bytes": (_sz, [_i, _i, _ip, _i, _i, _i]),
