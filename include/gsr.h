@@ -618,6 +618,10 @@ int gsr_sugar_mesh_backward(int V, int F, int G, int N, const float* verts, cons
  *                  r = S_r / m;   e = S_d / m;   vert_xyz = R(r) p + 2 vec(e (x) conj(r))   (no antipodal sign fix)
  *   GSR_SKIN_LBS:  vert_xyz = sum w_k (R(q^_k) (p - node_xyz_k) + node_xyz_k + trans_k)
  *   both:          vert_rot = Exp(sum w_k Log(q_k)) (xyzw, unit, w >= 0);   vert_scale = sum w_k node_scales_k
+ * A deliberate deviation in GSR_SKIN_LBS: the reference passes q_k to pypose's matrix() as it is, this header
+ * normalises it first (as the reference's own "dqs" branch does).  On unit quaternions the values are equal; the
+ * derivative along q_k (the quaternion's norm) is 0 here and 2 (R - I)(p - node_xyz_k) for a matrix() that does not
+ * normalise.  tests/test_reference_pins.py compares that gradient without its component along q_k.
  * Outputs vert_xyz (T,V,3), vert_rot (T,V,4) 16-byte aligned, vert_scale (T,V,3) (required iff node_scales is given).
  * Backward: the exact derivative.  dL_dxyz (T,V,3), dL_drot (T,V,4), dL_dscale (T,V,3): any may be NULL (zero).
  * Writes in full dL_dverts (V,3), dL_dnode_trans (T,P,3), dL_dnode_rots (T,P,4) (through the normalisation) and, iff
