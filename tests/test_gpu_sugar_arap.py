@@ -20,9 +20,7 @@ torch = pytest.importorskip("torch")
 import gsr_synthetic as gs  # noqa: E402
 import sugar_arap_reference as ref  # noqa: E402
 import sugar_dynamic_reference as dyn_ref  # noqa: E402
-from test_gpu_sugar_dynamic import _rel  # noqa: E402
-from test_sugar_arap import jittered_icosphere, mesh  # noqa: E402
-from test_sugar_dynamic import random_quats  # noqa: E402
+from sugar_cases import _rel, jittered_icosphere, mesh, random_quats  # noqa: E402
 
 FORMS = ("quat", "matrix")
 ENERGY_FLOOR = 2.0 ** -23

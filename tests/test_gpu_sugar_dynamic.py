@@ -19,15 +19,9 @@ torch = pytest.importorskip("torch")
 
 import gsr_synthetic as gs  # noqa: E402
 import sugar_dynamic_reference as ref  # noqa: E402
-from test_gpu_sugar_mesh import _fan  # noqa: E402
-from test_sugar_dynamic import random_quats  # noqa: E402
+from sugar_cases import _fan, _rel, random_quats  # noqa: E402
 
 THICKNESS = 3.5e-6
-
-
-def _rel(a, b):
-    scale = float(b.double().abs().max()) if b.numel() else 0.0
-    return float((a.double() - b.double()).abs().max()) / scale if scale > 0 else 0.0
 
 
 def _check(got, r64, r32, keys, tag):

@@ -20,13 +20,9 @@ torch = pytest.importorskip("torch")
 
 import gsr_synthetic as gs  # noqa: E402
 import sugar_mesh_reference as ref  # noqa: E402
+from sugar_cases import _fan, _rel  # noqa: E402
 
 THICKNESS = 3.5e-6
-
-
-def _rel(a, b):
-    scale = float(b.double().abs().max()) if b.numel() else 0.0
-    return float((a.double() - b.double()).abs().max()) / scale if scale > 0 else 0.0
 
 
 class _Case:
@@ -111,15 +107,6 @@ def _ico3():
 @functools.lru_cache(maxsize=None)
 def _ico3_gpu():
     return _ico3().gpu()
-
-
-def _fan(n=200):
-    """n faces around vertex 0 (a closed, slightly crumpled fan) and one extra vertex no face uses."""
-    ang = np.arange(n) * (2 * np.pi / n)
-    ring = np.stack([np.cos(ang), np.sin(ang), 0.1 * np.sin(7 * ang)], 1)
-    verts = np.concatenate([[[0.0, 0.0, 0.3]], ring, [[2.0, 2.0, 2.0]]])
-    faces = np.stack([np.zeros(n, np.int64), 1 + np.arange(n), 1 + (np.arange(n) + 1) % n], 1)
-    return verts, faces
 
 
 @pytest.mark.gpu

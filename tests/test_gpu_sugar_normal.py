@@ -66,7 +66,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from test_gpu_sugar_field import EPS, M_FULL, N_EXTRA, N_REF, _field, _mask, _ratios, _scene  # noqa: E402
+from sugar_cases import EPS, M_FULL, N_EXTRA, N_REF, _field, _mask, _ratios, _scene  # noqa: E402
 
 WMIN = 1e-6
 DENORM = 2.0 ** -149  # the spacing of fp32 below 2^-126
@@ -357,7 +357,7 @@ def test_coarse_density_regulation(monkeypatch):
         r = (1 - W / Wc) n_i + sum_k wh_k (n_i - s_k n_j),  dr_c <= P_c = 2 rho sum_k wh_k |n_i - s_k n_j|_c +
         rho [W < 1e-6] (W / Wc) |n_i,c|,  d(loss) <= 2 |r| . P + P . P."""
     import sugar_field
-    from test_gpu_sugar_field import _full_case as _field_full_case
+    from sugar_cases import _full_case as _field_full_case
 
     sc = _scene()
     g = torch.Generator().manual_seed(11)

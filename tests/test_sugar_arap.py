@@ -2,61 +2,19 @@
 (V, V) restatement of tests/sugar_arap_reference.py (bitwise: both sides run the same torch float32 ops on this
 machine), the argument checks, and the properties that pin the energy restatement (the checker of the GPU tests in
 tests/test_gpu_sugar_arap.py)."""
-import numpy as np
 import pytest
 
 from diff_gaussian_rasterization import _C
 
 torch = pytest.importorskip("torch")
 
-import gsr_synthetic as gs  # noqa: E402
 import sugar_arap  # noqa: E402
 import sugar_arap_reference as ref  # noqa: E402
 from sugar_arap import ArapBinding, arap_energy  # noqa: E402
-from test_gpu_sugar_mesh import _fan  # noqa: E402
-from test_sugar_dynamic import random_quats  # noqa: E402
+from sugar_cases import MESHES, mesh, random_quats  # noqa: E402
 
 NAMES = ("gsr_sugar_arap_workspace_bytes", "gsr_sugar_arap_forward", "gsr_sugar_arap_backward")
 D = torch.float64
-
-TRIANGLE = ([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [-0.5, 0.4, 0.1]], [[0, 1, 2]])  # obtuse at vertex 0
-TETRAHEDRON = ([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [-0.8, 0.4, 0.0], [0.1, 0.4, 1.0]],  # closed; obtuse at vertex 0
-               [[0, 1, 2], [0, 3, 1], [1, 3, 2], [2, 3, 0]])
-
-
-def jittered_icosphere(subdiv, amount=0.45, seed=0):
-    """The icosphere with its vertices moved by `amount` of the mean edge length: some corners become obtuse."""
-    v, f = gs.icosphere(subdiv)
-    edge = np.linalg.norm(v[f[:, 0]] - v[f[:, 1]], axis=1).mean()
-    return v + amount * edge * np.random.default_rng(seed).uniform(-1, 1, v.shape), f
-
-
-def open_fan(n=7):
-    """n faces around vertex 0 that do not close: the rim's two ends have valence 2.  Every other rim vertex is pulled
-    in, so the corners there are obtuse."""
-    ang = np.arange(n + 1) * 0.5
-    rad = 1.0 - 0.6 * (np.arange(n + 1) % 2)
-    ring = np.stack([rad * np.cos(ang), rad * np.sin(ang), 0.2 * np.sin(3 * ang)], 1)
-    return np.concatenate([[[0.0, 0.0, 0.3]], ring]), np.stack([np.zeros(n, np.int64), 1 + np.arange(n),
-                                                                2 + np.arange(n)], 1)
-
-
-def isolated_and_degenerate():
-    """A jittered icosphere(0), vertex 12 in no face, and a collinear (zero-area) face on three vertices of its own."""
-    v, f = jittered_icosphere(0, seed=3)
-    extra = [[2.0, 2.0, 2.0], [1.0, 1.0, 1.0], [1.01, 1.0, 1.0], [1.02, 1.0, 1.0]]
-    return np.concatenate([v, extra]), np.concatenate([f, [[13, 14, 15]]])
-
-
-MESHES = {"triangle": lambda: TRIANGLE, "tetrahedron": lambda: TETRAHEDRON,
-          "icosphere1": lambda: jittered_icosphere(1), "open_fan": open_fan, "fan200": lambda: _fan(200),
-          "isolated_degenerate": isolated_and_degenerate}
-
-
-def mesh(name):
-    v, f = MESHES[name]()
-    return torch.as_tensor(np.asarray(v), dtype=torch.float32), torch.as_tensor(np.asarray(f), dtype=torch.int64)
-
 
 def test_library_has_the_entry_points_at_abi_8():
     lib = _C.load_library()

@@ -15,24 +15,12 @@ import gsr_synthetic as gs  # noqa: E402
 import sugar_dynamic  # noqa: E402
 import sugar_dynamic_reference as ref  # noqa: E402
 from sugar_dynamic import SkinBinding, skin_vertices, timed_gaussians  # noqa: E402
+from sugar_cases import random_quats  # noqa: E402
 from sugar_mesh import MeshBinding  # noqa: E402
 
 NAMES = ("gsr_sugar_skin_workspace_bytes", "gsr_sugar_skin_forward", "gsr_sugar_skin_backward",
          "gsr_sugar_timed_workspace_bytes", "gsr_sugar_timed_forward", "gsr_sugar_timed_backward")
 D = torch.float64
-
-
-def random_quats(gen, shape, dtype=torch.float32, max_angle=2.6, identity_every=7):
-    """(x, y, z, w) quaternions: rotation angles within +-max_angle, both signs of w, norms in [0.5, 1.5], every
-    identity_every-th row exactly the identity."""
-    axis = torch.nn.functional.normalize(torch.randn(*shape, 3, generator=gen, dtype=D), dim=-1)
-    ang = (torch.rand(*shape, 1, generator=gen, dtype=D) * 2 - 1) * max_angle
-    q = torch.cat([axis * torch.sin(ang / 2), torch.cos(ang / 2)], -1)
-    sign = torch.where(torch.rand(*shape, 1, generator=gen) < 0.5, -1.0, 1.0).to(D)
-    q = q * sign * (0.5 + torch.rand(*shape, 1, generator=gen, dtype=D))
-    if identity_every:
-        q.view(-1, 4)[::identity_every] = torch.tensor([0., 0., 0., 1.], dtype=D)
-    return q.to(dtype).contiguous()
 
 
 def test_library_has_the_entry_points_at_abi_8():

@@ -16,14 +16,13 @@
 //                    every term of its gradient: a gather, no atomics.
 // Long rows: a lane walks a row of at most GSR_ARAP_LANE_ROW entries itself.  A longer row (a fan hub) is left for
 // the lane's wave: after the short rows, the wave takes its long rows one by one in lane order, lane l adding entries
-// l, l + 64, ... of the row, and the 64 partial sums are added by a butterfly; the row's lane keeps the result.  So a
+// l, l + 64, ... of the row, and the 64 partial sums are added by wave_sum_f64's butterfly; the row's lane keeps it.  So a
 // hub of valence n costs its wave n / 64 rounds, not n.
 // No atomics: every sum's order is fixed by the input.
 #include <math.h>
 
-#include "../../include/gsr.h"
 #include "gsr_kernels.h"
-#include "gsr_math.h"
+#include "gsr_sugar.h"
 
 namespace gsr {
 
@@ -140,17 +139,11 @@ GSR_HD void arap_store_zero(const ArapCall& a, size_t tv, float* dxyz, float* dr
   for (int k = 0; k < n; ++k) drot[(size_t)n * tv + k] = 0.0f;
 }
 
-__device__ __forceinline__ double arap_wave_sum(double x) {  // the same bits in every lane: a + b = b + a
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
-__device__ __forceinline__ void arap_wave_sum(ArapAcc<false>& c) { c.e = arap_wave_sum(c.e); }
+__device__ __forceinline__ void arap_wave_sum(ArapAcc<false>& c) { c.e = wave_sum_f64(c.e); }
 __device__ __forceinline__ void arap_wave_sum(ArapAcc<true>& c) {
-  c.gx = d3(arap_wave_sum(c.gx.x), arap_wave_sum(c.gx.y), arap_wave_sum(c.gx.z));
+  c.gx = wave_sum_d3(c.gx);
 #pragma unroll
-  for (int r = 0; r < 3; ++r)
-    c.G.r[r] = d3(arap_wave_sum(c.G.r[r].x), arap_wave_sum(c.G.r[r].y), arap_wave_sum(c.G.r[r].z));
+  for (int r = 0; r < 3; ++r) c.G.r[r] = wave_sum_d3(c.G.r[r]);
 }
 
 // The row sums of vertex v at frame t (valid = v < V; every lane of the wave calls this, valid or not).  b .. e: the
@@ -161,9 +154,7 @@ __device__ __forceinline__ void arap_rows(const ArapCall& a, int t, int v, bool 
   arap_zero(acc);
   b = e = 0;
   if (valid) {
-    b = a.offsets[v], e = a.offsets[v + 1];
-    b = b < 0 ? 0 : b;
-    e = e > a.E ? a.E : e;
+    row_range(a.offsets, v, a.E, b, e);
     e = e < b ? b : e;
   }
   const bool is_long = e - b > GSR_ARAP_LANE_ROW;
@@ -195,7 +186,7 @@ __global__ __launch_bounds__(GSR_ARAP_BLOCK) void k_arap_forward(ArapCall a, int
   long long b, e;
   ArapAcc<false> acc;
   arap_rows<false>(a, t, v, v < a.V, b, e, acc);
-  const double s = arap_wave_sum(acc.e);
+  const double s = wave_sum_f64(acc.e);
   if ((threadIdx.x & 63) == 0) wave_e[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -211,7 +202,7 @@ __global__ __launch_bounds__(64) void k_arap_reduce(int blocks_per_frame, const 
   const double* p = partial + (size_t)blockIdx.x * blocks_per_frame;
   double s = 0.0;
   for (int k = threadIdx.x; k < blocks_per_frame; k += 64) s += p[k];
-  s = arap_wave_sum(s);
+  s = wave_sum_f64(s);
   if (threadIdx.x == 0) energy[blockIdx.x] = (float)s;
 }
 

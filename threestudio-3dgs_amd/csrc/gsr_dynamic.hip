@@ -23,13 +23,14 @@
 //   k_timed_vertex   one lane per (t, vertex): adds its corner rows in corner_order.
 //   k_timed_gauss    one lane per Gaussian: recomputes its rotation for t = 0 .. T-1 and adds dL/drotation0 and
 //                    dL/dlog_scales in that order.
+// The face normal and its adjoint, the barycentric table, the rows of the two incidence tables (corner_order,
+// item_order) and the fp64 butterfly are those of gsr_sugar.h, shared with gsr_mesh.hip and gsr_arap.hip.
 // No atomics: every sum's order is fixed by the input.  The bodies are host-callable functions of an item index (the
 // kernels only derive the index), so they can be stepped through on the CPU.
 #include <math.h>
 
-#include "../../include/gsr.h"
 #include "gsr_kernels.h"
-#include "gsr_math.h"
+#include "gsr_sugar.h"
 
 namespace gsr {
 
@@ -216,16 +217,6 @@ __global__ __launch_bounds__(256) void k_skin_verts_sum(int T, int V, const floa
   store3(dverts + 3 * (size_t)v, s);
 }
 
-__device__ __forceinline__ double wave_sum_f64(double x) {  // the same bits in every lane: a + b = b + a
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
-__device__ __forceinline__ D3 wave_sum_d3(D3 a) {
-  return d3(wave_sum_f64(a.x), wave_sum_f64(a.y), wave_sum_f64(a.z));
-}
-__device__ __forceinline__ Q4 wave_sum_q4(Q4 a) { return q4(wave_sum_d3(a.v), wave_sum_f64(a.w)); }
-
 __global__ __launch_bounds__(64) void k_skin_node(SkinCall a, const double* __restrict__ nodes,
                                                   const int* __restrict__ item_order,
                                                   const int* __restrict__ node_offsets,
@@ -235,15 +226,14 @@ __global__ __launch_bounds__(64) void k_skin_node(SkinCall a, const double* __re
   const long long i = blockIdx.x;  // t P + node
   const int t = (int)(i / a.P), j = (int)(i % a.P);
   const long long n = (long long)a.V * a.K;
-  long long b = node_offsets[j], e = node_offsets[j + 1];
-  b = b < 0 ? 0 : b;
-  e = e > n ? n : e;
+  long long b, e;
+  row_range(node_offsets, j, n, b, e);
   SkinNodeAcc acc;
   acc.A = acc.B = qzero();
   acc.C = acc.D = d3(0.0, 0.0, 0.0);
   for (long long k = b + threadIdx.x; k < e; k += 64) {
     const int item = item_order[k];
-    if ((unsigned)item >= (unsigned)n) continue;  // not an item: skipped
+    if (!in_range(item, n)) continue;  // not an item: skipped
     skin_node_item(a, nodes, t, j, item, rows, g_xyz, g_scale, acc);
   }
   acc.A = wave_sum_q4(acc.A);
@@ -286,24 +276,15 @@ void launch_skin_backward(const SkinCall& c, const int* item_order, const int* n
 }
 
 // ---- timed Gaussians --------------------------------------------------------------------------------------------
-struct TimedBary {
-  float w[GSR_MESH_MAX_G][3];
-};
-
 // a face at frame t: its corners' positions, rotations (and their Logs) and scales, the normal's chain
-struct TimedFace {
+struct TimedFace : FaceNormal {
   int i[3];
   D3 p[3], L[3], s[3];
   Q4 q[3];
-  D3 c, n, R0;
 };
 // false (nothing dereferenced) when a face entry is outside [0, V)
 GSR_HD bool timed_face(const TimedCall& a, int t, int f, bool normal, TimedFace& fc) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    fc.i[c] = a.faces[3 * (size_t)f + c];
-    if ((unsigned)fc.i[c] >= (unsigned)a.V) return false;
-  }
+  if (!face_corners(a.faces, a.V, f, fc.i)) return false;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const size_t tv = (size_t)t * a.V + fc.i[c];
@@ -312,14 +293,10 @@ GSR_HD bool timed_face(const TimedCall& a, int t, int f, bool normal, TimedFace&
     fc.L[c] = qlog(fc.q[c]);
     fc.s[c] = a.vert_scale != nullptr ? load3(a.vert_scale + 3 * tv) : d3(0.0, 0.0, 0.0);
   }
-  if (normal) {  // as gsr_sugar_mesh_forward
-    fc.c = cross(fc.p[1] - fc.p[0], fc.p[2] - fc.p[0]);
-    fc.n = normalize(fc.c, 1e-6);
-    fc.R0 = normalize(fc.n, 1e-12);
-  }
+  if (normal) static_cast<FaceNormal&>(fc) = face_normal(fc.p[0], fc.p[1], fc.p[2]);
   return true;
 }
-GSR_HD D3 bary_mix(const TimedBary& b, int g, const D3* x) {
+GSR_HD D3 bary_mix(const FaceBary& b, int g, const D3* x) {
   return (double)b.w[g][0] * x[0] + (double)b.w[g][1] * x[1] + (double)b.w[g][2] * x[2];
 }
 // Q = Exp(phi) (x) q0 before its normalisation
@@ -328,7 +305,7 @@ struct TimedRot {
   Q4 E, q0, Q;
   double len;
 };
-GSR_HD TimedRot timed_rot(const TimedCall& a, const TimedBary& b, const TimedFace& fc, int g, size_t n) {
+GSR_HD TimedRot timed_rot(const TimedCall& a, const FaceBary& b, const TimedFace& fc, int g, size_t n) {
   TimedRot r;
   r.phi = bary_mix(b, g, fc.L);
   r.E = qexp(r.phi);
@@ -345,7 +322,7 @@ GSR_HD Q4 timed_rot_grad(const TimedRot& r, const float* g_rotation) {
   return (1.0 / r.len) * (gu + (-dot(u, gu)) * u);
 }
 
-GSR_HD void timed_face_forward(const TimedCall& a, const TimedBary& b, long long i, float* xyz, float* rotation,
+GSR_HD void timed_face_forward(const TimedCall& a, const FaceBary& b, long long i, float* xyz, float* rotation,
                                float* normals, float* scaling) {  // i = t F + f
   const int t = (int)(i / a.F), f = (int)(i % a.F);
   const size_t N = (size_t)a.F * a.G;
@@ -379,7 +356,7 @@ struct TimedGrads {
   const float *g_xyz, *g_rotation, *g_normals, *g_scaling;  // any may be null (zero)
 };
 
-GSR_HD void timed_face_backward(const TimedCall& a, const TimedBary& b, const TimedGrads& up, long long i,
+GSR_HD void timed_face_backward(const TimedCall& a, const FaceBary& b, const TimedGrads& up, long long i,
                                 float* rows) {  // i = t F + f
   const int t = (int)(i / a.F), f = (int)(i % a.F);
   const size_t N = (size_t)a.F * a.G;
@@ -418,13 +395,7 @@ GSR_HD void timed_face_backward(const TimedCall& a, const TimedBary& b, const Ti
       for (int c = 0; c < 3; ++c) gs[c] = gs[c] + w[c] * gv;
     }
   }
-  if (up.g_normals != nullptr) {  // R0 = normalize(n), n = normalize(c), c = (p1 - p0) x (p2 - p0)
-    const D3 gc = normalize_grad(normalize_grad(gR0, fc.n, 1e-12), fc.c, 1e-6);
-    const D3 ge1 = cross(fc.p[2] - fc.p[0], gc), ge2 = cross(gc, fc.p[1] - fc.p[0]);
-    gp[1] = gp[1] + ge1;
-    gp[2] = gp[2] + ge2;
-    gp[0] = gp[0] - (ge1 + ge2);
-  }
+  if (up.g_normals != nullptr) face_normal_grad(fc, fc.p[0], fc.p[1], fc.p[2], gR0, gp[0], gp[1], gp[2]);
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     float* r = row + GSR_TIMED_ROW * c;
@@ -439,15 +410,14 @@ GSR_HD void timed_vertex_backward(int T, int V, int F, long long i, const int* c
                                   const float* rows, float* dxyz, float* drot, float* dscale) {  // i = t V + v
   const int t = (int)(i / V), v = (int)(i % V);
   const long long n = 3ll * F;
-  long long b = vert_offsets[v], e = vert_offsets[v + 1];
-  b = b < 0 ? 0 : b;
-  e = e > n ? n : e;
+  long long b, e;
+  row_range(vert_offsets, v, n, b, e);
   D3 sp = d3(0.0, 0.0, 0.0), ss = sp;
   Q4 sq = qzero();
   const float* base = rows + 3 * GSR_TIMED_ROW * (size_t)t * (size_t)F;
   for (long long k = b; k < e; ++k) {
     const int co = corner_order[k];
-    if ((unsigned)co >= (unsigned)n) continue;  // not a corner: skipped
+    if (!in_range(co, n)) continue;  // not a corner: skipped
     const float* r = base + GSR_TIMED_ROW * (size_t)co;
     sp = sp + load3(r);
     sq = sq + load_q_row(r + 3);
@@ -458,7 +428,7 @@ GSR_HD void timed_vertex_backward(int T, int V, int F, long long i, const int* c
   if (dscale != nullptr) store3(dscale + 3 * i, ss);
 }
 
-GSR_HD void timed_gauss_backward(const TimedCall& a, const TimedBary& b, const TimedGrads& up, long long n,
+GSR_HD void timed_gauss_backward(const TimedCall& a, const FaceBary& b, const TimedGrads& up, long long n,
                                  float* drotation0, float* dlog_scales) {  // n = f G + g
   const int f = (int)(n / a.G), g = (int)(n % a.G);
   const size_t N = (size_t)a.F * a.G;
@@ -486,14 +456,14 @@ GSR_HD void timed_gauss_backward(const TimedCall& a, const TimedBary& b, const T
   if (dlog_scales != nullptr) ((float2*)dlog_scales)[n] = make_float2((float)gl0, (float)gl1);
 }
 
-__global__ __launch_bounds__(256) void k_timed_forward(TimedCall a, TimedBary b, float* __restrict__ xyz,
+__global__ __launch_bounds__(256) void k_timed_forward(TimedCall a, FaceBary b, float* __restrict__ xyz,
                                                        float* __restrict__ rotation, float* __restrict__ normals,
                                                        float* __restrict__ scaling) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i < (long long)a.T * a.F) timed_face_forward(a, b, i, xyz, rotation, normals, scaling);
 }
 
-__global__ __launch_bounds__(256) void k_timed_face(TimedCall a, TimedBary b, TimedGrads up,
+__global__ __launch_bounds__(256) void k_timed_face(TimedCall a, FaceBary b, TimedGrads up,
                                                     float* __restrict__ rows) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i < (long long)a.T * a.F) timed_face_backward(a, b, up, i, rows);
@@ -507,7 +477,7 @@ __global__ __launch_bounds__(256) void k_timed_vertex(int T, int V, int F, const
   if (i < (long long)T * V) timed_vertex_backward(T, V, F, i, corner_order, vert_offsets, rows, dxyz, drot, dscale);
 }
 
-__global__ __launch_bounds__(256) void k_timed_gauss(TimedCall a, TimedBary b, TimedGrads up,
+__global__ __launch_bounds__(256) void k_timed_gauss(TimedCall a, FaceBary b, TimedGrads up,
                                                      float* __restrict__ drotation0,
                                                      float* __restrict__ dlog_scales) {
   const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -518,17 +488,10 @@ size_t timed_workspace_bytes(int T, int F) {
   return align_up(sizeof(float) * 3 * GSR_TIMED_ROW * (size_t)(T > 0 ? T : 1) * (size_t)(F > 0 ? F : 1), 256);
 }
 
-static TimedBary timed_bary(int G, const float* bary) {  // (host memory: it travels in the kernel arguments)
-  TimedBary b{};
-  for (int g = 0; g < G; ++g)
-    for (int k = 0; k < 3; ++k) b.w[g][k] = bary[3 * g + k];
-  return b;
-}
-
 void launch_timed_forward(const TimedCall& c, const float* bary, float* xyz, float* rotation, float* normals,
                           float* scaling, hipStream_t stream) {
   hipLaunchKernelGGL(k_timed_forward, dim3(div_up((long long)c.T * c.F, 256)), dim3(256), 0, stream, c,
-                     timed_bary(c.G, bary), xyz, rotation, normals, c.vert_scale != nullptr ? scaling : nullptr);
+                     face_bary(c.G, bary), xyz, rotation, normals, c.vert_scale != nullptr ? scaling : nullptr);
 }
 
 void launch_timed_backward(const TimedCall& c, const float* bary, const int* corner_order, const int* vert_offsets,
@@ -536,7 +499,7 @@ void launch_timed_backward(const TimedCall& c, const float* bary, const int* cor
                            const float* g_scaling, float* dvert_xyz, float* dvert_rot, float* drotation0,
                            float* dvert_scale, float* dlog_scales, void* workspace, hipStream_t stream) {
   float* rows = (float*)workspace;
-  const TimedBary b = timed_bary(c.G, bary);
+  const FaceBary b = face_bary(c.G, bary);
   const TimedGrads up{g_xyz, g_rotation, g_normals, g_scaling};
   const bool scales = c.vert_scale != nullptr;
   hipLaunchKernelGGL(k_timed_face, dim3(div_up((long long)c.T * c.F, 256)), dim3(256), 0, stream, c, b, up, rows);

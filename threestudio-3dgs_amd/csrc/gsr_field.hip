@@ -11,12 +11,12 @@
 //   k_field_pack    one 64-byte record per Gaussian (c | strength, A, min_scale): a neighbour is one aligned line
 //                   instead of pieces of four arrays with 12 / 36 / 4 / 4-byte strides.
 //   k_field_sample  16 lanes per sample (4 samples per wave), lane l owns slots k = l and l + 16; the K-sums are an
-//                   xor butterfly over the 16 lanes (one DPP row).  Forward: density, beta_avg, op.  Backward
+//                   xor butterfly over the 16 lanes (group_sum, gsr_wave.h).  Forward: density, beta_avg, op.  Backward
 //                   (recomputed, nothing M x K kept from the forward): dL/dx by the same butterfly, and the sort key
 //                   of every pair (its Gaussian, or N when the pair contributes nothing).
-//   k_field_bounds  [begin, end) of every Gaussian's run in the sorted keys.
+//   sort_runs       (gsr_sort.hip) the stable sort of the keys and k_run_bounds: [begin, end) of every Gaussian's run.
 //   k_field_gauss   L lanes (16 or 64) per Gaussian walk its run in pair order, L pairs at a time, recompute the pair
-//                   and add into per-lane sums; the L lanes are combined by an xor butterfly.  No atomics anywhere:
+//                   and add into per-lane sums; the L lanes are combined by the same butterfly.  No atomics anywhere:
 //                   every sum's order is fixed by the input (stable sort: pairs of one Gaussian ascend by m K + k).
 #include <math.h>
 
@@ -28,11 +28,8 @@ namespace gsr {
 #define GSR_FIELD_QMAX 1e8f
 
 struct FieldWork {
-  float4* pack;       // [N][4]
-  uint32_t* keys[2];  // [M K] each
-  uint32_t* vals[2];
-  uint32_t *counts, *totals;
-  uint32_t* bounds;  // begin [N], end [N]
+  float4* pack;  // [N][4]
+  RunWork run;   // of the M K pairs
   static FieldWork carve(void* base, long long M, int K, int N, size_t* bytes) {
     Carver c(base);
     FieldWork w;
@@ -42,11 +39,7 @@ struct FieldWork {
       *bytes = align_up(c.off, 256);
       return w;
     }
-    for (int i = 0; i < 2; ++i) w.keys[i] = c.take<uint32_t>(mk);
-    for (int i = 0; i < 2; ++i) w.vals[i] = c.take<uint32_t>(mk);
-    w.counts = c.take<uint32_t>((size_t)GSR_RADIX * (size_t)div_up((long long)mk, GSR_SORT_TILE));
-    w.totals = c.take<uint32_t>((size_t)GSR_RADIX);
-    w.bounds = c.take<uint32_t>(2 * n);
+    w.run.carve(c, mk, n);
     if (bytes) *bytes = align_up(c.off, 256);
     return w;
   }
@@ -108,13 +101,6 @@ __device__ __forceinline__ void field_pair_dw(const FieldPair& p, float dop, flo
   dw0 = p.pass ? p.w0 * dq2 : 0.0f;
   dw1 = p.pass ? p.w1 * dq2 : 0.0f;
   dw2 = p.pass ? p.w2 * dq2 : 0.0f;
-}
-
-template <int L>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = L / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 struct FieldArgs {
@@ -193,16 +179,6 @@ __global__ __launch_bounds__(256) void k_field_sample(FieldArgs a, float* __rest
       dx[3 * m + 2] = s2;
     }
   }
-}
-
-__global__ __launch_bounds__(256) void k_field_bounds(const uint32_t* __restrict__ keys, uint32_t n, uint32_t N,
-                                                      uint32_t* __restrict__ begin, uint32_t* __restrict__ end) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)n) return;
-  const uint32_t key = keys[i];
-  if (key >= N) return;
-  if (i == 0 || keys[i - 1] != key) begin[key] = (uint32_t)i;
-  if (i + 1 == (long long)n || keys[i + 1] != key) end[key] = (uint32_t)i + 1u;
 }
 
 struct FieldGaussArgs {
@@ -319,22 +295,11 @@ int launch_field_backward(const FieldCall& c, const float* g_density, const floa
   FieldWork w = FieldWork::carve(workspace, c.M, c.K, c.N, nullptr);
   field_pack(c, w.pack, stream);
   hipLaunchKernelGGL((k_field_sample<true>), dim3(div_up(c.M, 16)), dim3(256), 0, stream, field_args(c, w.pack),
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr, g_density, g_op, dx, w.keys[0]);
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr, g_density, g_op, dx, w.run.keys[0]);
   if (c.N <= 0) return 0;
-  const uint32_t n = (uint32_t)((long long)c.M * c.K);
-  hipError_t err = hipMemsetAsync(w.bounds, 0, sizeof(uint32_t) * 2 * (size_t)c.N, stream);
-  if (err != hipSuccess) return (int)err;
-  SegInfo seg;
-  seg.V = 1;
-  seg.n[0] = n;
-  seg.start[0] = 0u;
-  int key_bits = 1;
-  while (key_bits < 32 && (1ull << key_bits) <= (unsigned long long)c.N) ++key_bits;  // keys 0 .. N
-  const int res = seg_sort(w.keys, w.vals, true, seg, 0, key_bits, w.counts, w.totals, stream);
-  uint32_t* begin = w.bounds;
-  uint32_t* end = w.bounds + c.N;
-  hipLaunchKernelGGL(k_field_bounds, dim3(div_up((long long)n, 256)), dim3(256), 0, stream, w.keys[res], n,
-                     (uint32_t)c.N, begin, end);
+  int res = 0;
+  const int err = sort_runs(w.run, (uint32_t)((long long)c.M * c.K), c.N, &res, stream);
+  if (err != 0) return err;
   FieldGaussArgs a;
   a.M = c.M;
   a.K = c.K;
@@ -344,9 +309,9 @@ int launch_field_backward(const FieldCall& c, const float* g_density, const floa
   a.inv_sr = c.inv_sr;
   a.strengths = c.strengths;
   a.density_factor = c.density_factor;
-  a.vals = w.vals[res];
-  a.begin = begin;
-  a.end = end;
+  a.vals = w.run.vals[res];
+  a.begin = w.run.bounds;
+  a.end = w.run.bounds + c.N;
   a.g_density = g_density;
   a.g_beta = g_beta;
   a.g_op = g_op;

@@ -14,6 +14,28 @@ namespace gsr {
 // RADIX x (total 4096-item blocks) words, totals RADIX x V.
 int seg_sort(uint32_t* keys[2], uint32_t* vals[2], bool vals_identity, SegInfo seg, int bit_lo, int key_bits,
              uint32_t* counts, uint32_t* totals, hipStream_t stream, int max_bits = GSR_RADIX_BITS);
+// Runs of equal keys (the per-Gaussian sums of gsr_field.hip and gsr_normal.hip): the buffers of one sort of `items`
+// keys in [0, N] and the bounds of the runs of the keys below N.
+struct RunWork {
+  uint32_t* keys[2];  // [items] each
+  uint32_t* vals[2];
+  uint32_t *counts, *totals;
+  uint32_t* bounds;  // begin [N], end [N]
+  // n = max(N, 1); coef: one float per item, carved between the values and the counts, or null
+  void carve(Carver& c, size_t items, size_t n, float** coef = nullptr) {
+    for (int i = 0; i < 2; ++i) keys[i] = c.take<uint32_t>(items);
+    for (int i = 0; i < 2; ++i) vals[i] = c.take<uint32_t>(items);
+    if (coef) *coef = c.take<float>(items);
+    counts = c.take<uint32_t>((size_t)GSR_RADIX * (size_t)div_up((long long)items, GSR_SORT_TILE));
+    totals = c.take<uint32_t>((size_t)GSR_RADIX);
+    bounds = c.take<uint32_t>(2 * n);
+  }
+};
+// Given n unsorted keys in w.keys[0] (N > 0): a stable sort with the positions as values (k_run_bounds: key N sorts
+// last and has no run), then begin = w.bounds and end = w.bounds + N hold the [begin, end) of every key's run in the
+// sorted order, 0 and 0 for an absent key.  *half: the index (0/1) of the keys / vals that hold the result.  Returns
+// 0, or the hipError_t of a failed stream operation.
+int sort_runs(RunWork w, uint32_t n, int N, int* half, hipStream_t stream);
 // The scatter's in-wave ranking: 1 = LDS-atomic ranks (the device was probed to service same-counter lanes in lane
 // order), 0 = ballot matching.  Decided once per process (gsr_sort.hip).
 int sort_rank_mode();

@@ -166,7 +166,7 @@ __device__ __forceinline__ float3 sh_to_rgb(int deg, const float* sh, const floa
   return make_float3(fmaxf(res.x, 0.0f), fmaxf(res.y, 0.0f), fmaxf(res.z, 0.0f));
 }
 
-// ---- fp64 vectors and quaternions of the SuGaR geometry kernels (gsr_mesh.hip, gsr_dynamic.hip) ----
+// ---- fp64 vectors and quaternions of the SuGaR geometry kernels (gsr_mesh.hip, gsr_dynamic.hip, gsr_arap.hip) ----
 // (host-callable too: the bodies of gsr_dynamic.hip can be stepped through on the CPU)
 #define GSR_HD __host__ __device__ __forceinline__
 struct D3 {

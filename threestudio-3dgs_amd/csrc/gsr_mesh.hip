@@ -3,7 +3,7 @@
 // vertex gather, the pytorch3d face normals, matrix_to_quaternion and the index_put scatter of the autograd backward).
 //
 // Gaussian f G + g belongs to face f with corners p0, p1, p2 (normalize(v, eps) = v / max(|v|, eps)):
-//     c = (p1 - p0) x (p2 - p0);  n = normalize(c, 1e-6);  R0 = normalize(n, 1e-12)
+//     c = (p1 - p0) x (p2 - p0);  n = normalize(c, 1e-6);  R0 = normalize(n, 1e-12)        (face_normal, gsr_sugar.h)
 //     b1 = normalize(p0 - p1, 1e-12);  b2 = normalize(R0 x b1, 1e-12)
 //     z = normalize(complex, 1e-12);  R1 = z0 b1 + z1 b2;  R2 = -z1 b1 + z0 b2;  q = matrix_to_quaternion([R0|R1|R2])
 //     xyz = sum_k bary[g][k] p_k;  scaling = (thickness, exp(log_scales));  rotation = normalize(q, 1e-12)
@@ -20,35 +20,33 @@
 //   k_mesh_face     one lane per face: rebuilds the frame once, walks the face's Gaussians in ascending g (writing
 //                   dL/dcomplex and dL/dlog_scales), sums their gradients to the frame and to the corners in that
 //                   order, carries the sum through the frame and stores three corner rows (36 bytes per face).
-//   k_mesh_vertex   one lane per vertex: adds its incident corner rows in corner_order, from 0, writes dL/dverts.
+//   k_mesh_vertex   one lane per vertex: adds its incident corner rows in corner_order (its row of the incidence
+//                   table: row_range, gsr_sugar.h), from 0, writes dL/dverts.
 // No atomics: every sum's order is fixed by the input.
 #include <math.h>
 
-#include "../../include/gsr.h"
 #include "gsr_kernels.h"
-#include "gsr_math.h"
+#include "gsr_sugar.h"
 
 namespace gsr {
 
-struct MeshFrame {
+struct MeshFrame : FaceNormal {
   D3 p0, p1, p2;
-  D3 c, n, R0, d, b1, m, b2;
+  D3 d, b1, m, b2;
 };
 
 // the face's corners; false (nothing dereferenced) when an index is outside [0, V)
 __device__ __forceinline__ bool mesh_corners(const MeshCall& a, int f, MeshFrame& fr) {
-  const int i0 = a.faces[3 * (size_t)f], i1 = a.faces[3 * (size_t)f + 1], i2 = a.faces[3 * (size_t)f + 2];
-  if ((unsigned)i0 >= (unsigned)a.V || (unsigned)i1 >= (unsigned)a.V || (unsigned)i2 >= (unsigned)a.V) return false;
-  fr.p0 = load3(a.verts + 3 * (size_t)i0);
-  fr.p1 = load3(a.verts + 3 * (size_t)i1);
-  fr.p2 = load3(a.verts + 3 * (size_t)i2);
+  int i[3];
+  if (!face_corners(a.faces, a.V, f, i)) return false;
+  fr.p0 = load3(a.verts + 3 * (size_t)i[0]);
+  fr.p1 = load3(a.verts + 3 * (size_t)i[1]);
+  fr.p2 = load3(a.verts + 3 * (size_t)i[2]);
   return true;
 }
 
 __device__ __forceinline__ void mesh_frame(MeshFrame& fr) {
-  fr.c = cross(fr.p1 - fr.p0, fr.p2 - fr.p0);
-  fr.n = normalize(fr.c, 1e-6);
-  fr.R0 = normalize(fr.n, 1e-12);
+  static_cast<FaceNormal&>(fr) = face_normal(fr.p0, fr.p1, fr.p2);
   fr.d = fr.p0 - fr.p1;
   fr.b1 = normalize(fr.d, 1e-12);
   fr.m = cross(fr.R0, fr.b1);
@@ -88,11 +86,7 @@ __device__ __forceinline__ MeshQuat mesh_quat(D3 R0, D3 R1, D3 R2) {
   return q;
 }
 
-struct MeshBary {
-  float w[GSR_MESH_MAX_G][3];
-};
-
-__global__ __launch_bounds__(256) void k_mesh_forward(MeshCall a, MeshBary bary, float thickness,
+__global__ __launch_bounds__(256) void k_mesh_forward(MeshCall a, FaceBary bary, float thickness,
                                                       float* __restrict__ xyz, float* __restrict__ scaling,
                                                       float4* __restrict__ rotation, float* __restrict__ normals) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -135,7 +129,7 @@ struct MeshGrads {
   const float *g_xyz, *g_scaling, *g_rotation, *g_normals;  // any may be null (zero)
 };
 
-__global__ __launch_bounds__(256) void k_mesh_face(MeshCall a, MeshBary bary, MeshGrads up,
+__global__ __launch_bounds__(256) void k_mesh_face(MeshCall a, FaceBary bary, MeshGrads up,
                                                    float2* __restrict__ dcplx, float2* __restrict__ dlog_scales,
                                                    float* __restrict__ rows) {
   const int f = blockIdx.x * 256 + threadIdx.x;
@@ -236,20 +230,14 @@ __global__ __launch_bounds__(256) void k_mesh_face(MeshCall a, MeshBary bary, Me
     }
     dcplx[i] = dz;
   }
-  // through the frame: b2 = normalize(m), m = R0 x b1, b1 = normalize(d), d = p0 - p1, R0 = normalize(n),
-  // n = normalize(c), c = (p1 - p0) x (p2 - p0)
+  // through the frame: b2 = normalize(m), m = R0 x b1, b1 = normalize(d), d = p0 - p1, then the normal's chain
   const D3 gm = normalize_grad(gb2, fr.m, 1e-12);
   gR0 = gR0 + cross(fr.b1, gm);
   gb1 = gb1 + cross(gm, fr.R0);
   const D3 gd = normalize_grad(gb1, fr.d, 1e-12);
   gp0 = gp0 + gd;
   gp1 = gp1 - gd;
-  const D3 gc = normalize_grad(normalize_grad(gR0, fr.n, 1e-12), fr.c, 1e-6);
-  const D3 e1 = fr.p1 - fr.p0, e2 = fr.p2 - fr.p0;
-  const D3 ge1 = cross(e2, gc), ge2 = cross(gc, e1);
-  gp1 = gp1 + ge1;
-  gp2 = gp2 + ge2;
-  gp0 = gp0 - (ge1 + ge2);
+  face_normal_grad(fr, fr.p0, fr.p1, fr.p2, gR0, gp0, gp1, gp2);
   store3(row, gp0);
   store3(row + 3, gp1);
   store3(row + 6, gp2);
@@ -261,13 +249,12 @@ __global__ __launch_bounds__(256) void k_mesh_vertex(int V, int F, const int* __
   const int v = blockIdx.x * 256 + threadIdx.x;
   if (v >= V) return;
   const long long n = 3ll * F;
-  long long b = vert_offsets[v], e = vert_offsets[v + 1];
-  b = b < 0 ? 0 : b;
-  e = e > n ? n : e;
+  long long b, e;
+  row_range(vert_offsets, v, n, b, e);
   D3 s = d3(0.0, 0.0, 0.0);
   for (long long i = b; i < e; ++i) {
     const int co = corner_order[i];
-    if ((unsigned)co >= (unsigned)n) continue;  // not a corner: skipped
+    if (!in_range(co, n)) continue;  // not a corner: skipped
     s = s + load3(rows + 3 * (size_t)co);
   }
   store3(dverts + 3 * (size_t)v, s);
@@ -278,17 +265,10 @@ size_t mesh_workspace_bytes(int F, int V) {
   return align_up(sizeof(float) * 9 * (size_t)(F > 0 ? F : 1), 256);
 }
 
-static MeshBary mesh_bary(int G, const float* bary) {  // (host memory: it travels in the kernel arguments)
-  MeshBary b{};
-  for (int g = 0; g < G; ++g)
-    for (int k = 0; k < 3; ++k) b.w[g][k] = bary[3 * g + k];
-  return b;
-}
-
 void launch_mesh_forward(const MeshCall& c, const float* bary, float thickness, float* xyz, float* scaling,
                          float* rotation, float* normals, hipStream_t stream) {
   const long long N = (long long)c.F * c.G;
-  hipLaunchKernelGGL(k_mesh_forward, dim3(div_up(N, 256)), dim3(256), 0, stream, c, mesh_bary(c.G, bary), thickness,
+  hipLaunchKernelGGL(k_mesh_forward, dim3(div_up(N, 256)), dim3(256), 0, stream, c, face_bary(c.G, bary), thickness,
                      xyz, scaling, (float4*)rotation, normals);
 }
 
@@ -296,7 +276,7 @@ void launch_mesh_backward(const MeshCall& c, const float* bary, const int* corne
                           const float* g_xyz, const float* g_scaling, const float* g_rotation, const float* g_normals,
                           float* dverts, float* dcplx, float* dlog_scales, void* workspace, hipStream_t stream) {
   float* rows = (float*)workspace;
-  hipLaunchKernelGGL(k_mesh_face, dim3(div_up(c.F, 256)), dim3(256), 0, stream, c, mesh_bary(c.G, bary),
+  hipLaunchKernelGGL(k_mesh_face, dim3(div_up(c.F, 256)), dim3(256), 0, stream, c, face_bary(c.G, bary),
                      MeshGrads{g_xyz, g_scaling, g_rotation, g_normals}, (float2*)dcplx, (float2*)dlog_scales, rows);
   if (c.V > 0)
     hipLaunchKernelGGL(k_mesh_vertex, dim3(div_up(c.V, 256)), dim3(256), 0, stream, c.V, c.F, corner_order,

@@ -15,10 +15,10 @@
 // Kernels:
 //   k_normal_pack    one 32-byte record per Gaussian (c | max(min_scale, 1e-6), n): a neighbour is one aligned
 //                    half line instead of pieces of three arrays.
-//   k_normal_sample  16 lanes per sample, lane l owns slots l and l + 16, sums by the field's xor butterfly.
+//   k_normal_sample  16 lanes per sample, lane l owns slots l and l + 16, sums by group_sum's xor butterfly.
 //                    Forward: loss and the (M, 4) record (r, Wc).  Backward: with that record, the coefficient and the
 //                    sort key of each of the sample's K + 1 gradient terms (slot K is the sample's own 2 g r).
-//   k_normal_bounds  [begin, end) of every Gaussian's run in the sorted keys.
+//   sort_runs        (gsr_sort.hip) the stable sort of the keys and k_run_bounds: [begin, end) of every Gaussian's run.
 //   k_normal_gauss   L lanes (16 or 64) per Gaussian walk its run in pair order: dL/dn += coef[p] r[m].
 // No atomics: every sum's order is fixed by the input (stable sort: the terms of one Gaussian ascend by m (K + 1) + k).
 #include <math.h>
@@ -32,12 +32,9 @@ namespace gsr {
 #define GSR_NORMAL_SMIN 1e-6f   // the clamp of the min scale
 
 struct NormalWork {
-  float4* pack;       // [N][2]
-  uint32_t* keys[2];  // [M (K + 1)] each
-  uint32_t* vals[2];
-  float* coef;        // [M (K + 1)]
-  uint32_t *counts, *totals;
-  uint32_t* bounds;  // begin [N], end [N]
+  float4* pack;  // [N][2]
+  RunWork run;   // of the M (K + 1) gradient terms
+  float* coef;   // [M (K + 1)]
   static NormalWork carve(void* base, long long M, int K, int N, size_t* bytes) {
     Carver c(base);
     NormalWork w;
@@ -47,12 +44,7 @@ struct NormalWork {
       *bytes = align_up(c.off, 256);
       return w;
     }
-    for (int i = 0; i < 2; ++i) w.keys[i] = c.take<uint32_t>(mk);
-    for (int i = 0; i < 2; ++i) w.vals[i] = c.take<uint32_t>(mk);
-    w.coef = c.take<float>(mk);
-    w.counts = c.take<uint32_t>((size_t)GSR_RADIX * (size_t)div_up((long long)mk, GSR_SORT_TILE));
-    w.totals = c.take<uint32_t>((size_t)GSR_RADIX);
-    w.bounds = c.take<uint32_t>(2 * n);
+    w.run.carve(c, mk, n, &w.coef);
     if (bytes) *bytes = align_up(c.off, 256);
     return w;
   }
@@ -86,13 +78,6 @@ __device__ __forceinline__ void normal_pair(float x0, float x1, float x2, const 
   const double d0 = (double)x0 - (double)rc.x, d1 = (double)x1 - (double)rc.y, d2 = (double)x2 - (double)rc.z;
   const float a = s != 0.0f ? (float)fabs(fma(d2, (double)rn.z, fma(d1, (double)rn.y, d0 * (double)rn.x))) : 0.0f;
   w = op * a / (rc.w * rc.w);
-}
-
-template <int L>
-__device__ __forceinline__ float normal_group_sum(float v) {
-#pragma unroll
-  for (int o = L / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 struct NormalArgs {
@@ -150,7 +135,7 @@ __global__ __launch_bounds__(256) void k_normal_sample(NormalArgs a, float* __re
   for (int h = 0; h < 2; ++h)
     if (valid[h]) normal_pair(x0, x1, x2, rc[h], rn[h], ni0, ni1, ni2, opv[h], s[h], w[h]);
   if (!BWD) {
-    const float W = normal_group_sum<16>(w[0] + w[1]);
+    const float W = group_sum<16>(w[0] + w[1]);
     const float Wc = fmaxf(W, GSR_NORMAL_WMIN);
     float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
 #pragma unroll
@@ -161,9 +146,9 @@ __global__ __launch_bounds__(256) void k_normal_sample(NormalArgs a, float* __re
       v1 = fmaf(wh, ni1 - s[h] * rn[h].y, v1);
       v2 = fmaf(wh, ni2 - s[h] * rn[h].z, v2);
     }
-    v0 = normal_group_sum<16>(v0);
-    v1 = normal_group_sum<16>(v1);
-    v2 = normal_group_sum<16>(v2);
+    v0 = group_sum<16>(v0);
+    v1 = group_sum<16>(v1);
+    v2 = group_sum<16>(v2);
     if (live && l == 0) {
       const float rest = W >= GSR_NORMAL_WMIN ? 0.0f : 1.0f - W / Wc;
       const float r0 = ok ? fmaf(rest, ni0, v0) : 0.0f;
@@ -188,16 +173,6 @@ __global__ __launch_bounds__(256) void k_normal_sample(NormalArgs a, float* __re
       coef[base + a.K] = ok ? g2 : 0.0f;
     }
   }
-}
-
-__global__ __launch_bounds__(256) void k_normal_bounds(const uint32_t* __restrict__ keys, uint32_t n, uint32_t N,
-                                                       uint32_t* __restrict__ begin, uint32_t* __restrict__ end) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)n) return;
-  const uint32_t key = keys[i];
-  if (key >= N) return;
-  if (i == 0 || keys[i - 1] != key) begin[key] = (uint32_t)i;
-  if (i + 1 == (long long)n || keys[i + 1] != key) end[key] = (uint32_t)i + 1u;
 }
 
 template <int L>
@@ -225,9 +200,9 @@ __global__ __launch_bounds__(256) void k_normal_gauss(int M, int K, int N, const
     d1 = fmaf(c, r.y, d1);
     d2 = fmaf(c, r.z, d2);
   }
-  d0 = normal_group_sum<L>(d0);
-  d1 = normal_group_sum<L>(d1);
-  d2 = normal_group_sum<L>(d2);
+  d0 = group_sum<L>(d0);
+  d1 = group_sum<L>(d1);
+  d2 = group_sum<L>(d2);
   if (live && l == 0) {
     dnormals[3 * g] = d0;
     dnormals[3 * g + 1] = d1;
@@ -271,27 +246,17 @@ int launch_normal_backward(const NormalCall& c, const float* rec, const float* g
   NormalWork w = NormalWork::carve(workspace, c.M, c.K, c.N, nullptr);
   normal_pack(c, w.pack, stream);
   hipLaunchKernelGGL((k_normal_sample<true>), dim3(div_up(c.M, 16)), dim3(256), 0, stream, normal_args(c, w.pack),
-                     (float*)nullptr, (float4*)rec, g_loss, w.keys[0], w.coef);
-  const uint32_t n = (uint32_t)((long long)c.M * (c.K + 1));
-  hipError_t err = hipMemsetAsync(w.bounds, 0, sizeof(uint32_t) * 2 * (size_t)c.N, stream);
-  if (err != hipSuccess) return (int)err;
-  SegInfo seg{};
-  seg.V = 1;
-  seg.n[0] = n;
-  seg.start[0] = 0u;
-  int key_bits = 1;
-  while (key_bits < 32 && (1ull << key_bits) <= (unsigned long long)c.N) ++key_bits;  // keys 0 .. N
-  const int res = seg_sort(w.keys, w.vals, true, seg, 0, key_bits, w.counts, w.totals, stream);
-  uint32_t* begin = w.bounds;
-  uint32_t* end = w.bounds + c.N;
-  hipLaunchKernelGGL(k_normal_bounds, dim3(div_up((long long)n, 256)), dim3(256), 0, stream, w.keys[res], n,
-                     (uint32_t)c.N, begin, end);
+                     (float*)nullptr, (float4*)rec, g_loss, w.run.keys[0], w.coef);
+  int res = 0;
+  const int err = sort_runs(w.run, (uint32_t)((long long)c.M * (c.K + 1)), c.N, &res, stream);
+  if (err != 0) return err;
+  const uint32_t *begin = w.run.bounds, *end = w.run.bounds + c.N;
   if (normal_gauss_lanes(c.M, c.K, c.N) == 64)
     hipLaunchKernelGGL((k_normal_gauss<64>), dim3(div_up((long long)c.N * 64, 256)), dim3(256), 0, stream, c.M, c.K,
-                       c.N, w.vals[res], begin, end, w.coef, (const float4*)rec, dnormals);
+                       c.N, w.run.vals[res], begin, end, w.coef, (const float4*)rec, dnormals);
   else
     hipLaunchKernelGGL((k_normal_gauss<16>), dim3(div_up((long long)c.N * 16, 256)), dim3(256), 0, stream, c.M, c.K,
-                       c.N, w.vals[res], begin, end, w.coef, (const float4*)rec, dnormals);
+                       c.N, w.run.vals[res], begin, end, w.coef, (const float4*)rec, dnormals);
   return 0;
 }
 

@@ -350,4 +350,29 @@ int seg_sort(uint32_t* keys[2], uint32_t* vals[2], bool vals_identity, SegInfo s
   return src;
 }
 
+__global__ __launch_bounds__(256) void k_run_bounds(const uint32_t* __restrict__ keys, uint32_t n, uint32_t N,
+                                                    uint32_t* __restrict__ begin, uint32_t* __restrict__ end) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)n) return;
+  const uint32_t key = keys[i];
+  if (key >= N) return;
+  if (i == 0 || keys[i - 1] != key) begin[key] = (uint32_t)i;
+  if (i + 1 == (long long)n || keys[i + 1] != key) end[key] = (uint32_t)i + 1u;
+}
+
+int sort_runs(RunWork w, uint32_t n, int N, int* half, hipStream_t stream) {
+  hipError_t err = hipMemsetAsync(w.bounds, 0, sizeof(uint32_t) * 2 * (size_t)N, stream);
+  if (err != hipSuccess) return (int)err;
+  SegInfo seg{};
+  seg.V = 1;
+  seg.n[0] = n;
+  seg.start[0] = 0u;
+  int key_bits = 1;
+  while (key_bits < 32 && (1ull << key_bits) <= (unsigned long long)N) ++key_bits;  // keys 0 .. N
+  *half = seg_sort(w.keys, w.vals, true, seg, 0, key_bits, w.counts, w.totals, stream);
+  hipLaunchKernelGGL(k_run_bounds, dim3(div_up((long long)n, 256)), dim3(256), 0, stream, w.keys[*half], n,
+                     (uint32_t)N, w.bounds, w.bounds + N);
+  return 0;
+}
+
 }  // namespace gsr

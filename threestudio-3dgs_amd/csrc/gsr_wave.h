@@ -31,6 +31,21 @@ __device__ __forceinline__ float wave_sum(float x) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
 }
 
+// Sum over each aligned group of L lanes (L a power of two, at most 64) by an xor butterfly: the same bits in every
+// lane of the group (a + b = b + a).  The SuGaR stages promise the bits of this order (not wave_sum's), in fp32 over
+// 16 or 64 lanes and in fp64 over the wave.
+template <int L>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int o = L / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
+
 // Lanes of this wave whose `bits`-bit digit equals ours (restricted to lanes with valid=true).
 __device__ __forceinline__ unsigned long long match_digit(uint32_t d, int bits, bool valid) {
   // per bit b: s = 0 / all ones from the lane's bit, x |= ballot ^ s on each 32-bit half (one v_bitop3 each:

@@ -21,17 +21,13 @@ from __future__ import annotations
 import torch
 
 from diff_gaussian_rasterization import _C as _gsr
-from sugar_dynamic import _float_tensor, _on_gpu, _ups, _workspace
-from sugar_mesh import _aligned
+from sugar_common import INT_DTYPES, Binding, aligned, float_tensor, on_gpu, row_offsets, ups, workspace
 
 __all__ = ["ArapBinding", "arap_energy", "ARAP_ROT_FORMS"]
 
 ARAP_ROT_FORMS = {"quat": 0, "matrix": 1}  # GSR_ARAP_QUAT, GSR_ARAP_MATRIX
 
-_INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
-
-
-class ArapBinding:
+class ArapBinding(Binding):
     """The one-rings of a rest mesh with the reference's edge weights, built once, in plain torch, without anything
     of size V x V.
 
@@ -49,12 +45,14 @@ class ArapBinding:
     ``to(device)`` moves it.
     """
 
+    _TENSORS = ("nbr", "offsets", "w", "p", "verts")
+
     def __init__(self, verts, faces):
         if not isinstance(verts, torch.Tensor) or not verts.is_floating_point():
             raise ValueError("verts must be a floating-point tensor")
         if verts.dim() != 2 or int(verts.shape[1]) != 3:
             raise ValueError(f"verts must have shape (V, 3), got {tuple(verts.shape)}")
-        if not isinstance(faces, torch.Tensor) or faces.dtype not in _INT_DTYPES:
+        if not isinstance(faces, torch.Tensor) or faces.dtype not in INT_DTYPES:
             raise ValueError("faces must be an integer tensor")
         if faces.dim() != 2 or int(faces.shape[1]) != 3:
             raise ValueError(f"faces must have shape (F, 3), got {tuple(faces.shape)}")
@@ -98,26 +96,13 @@ class ArapBinding:
             return torch.where(key[pos] == k, val[pos], torch.zeros_like(val[pos]))
 
         counts = torch.bincount(ii, minlength=V)
-        offsets = torch.zeros(V + 1, dtype=torch.int64, device=verts.device)
-        offsets[1:] = torch.cumsum(counts, 0)
-        self.offsets = offsets.to(torch.int32).contiguous()
+        self.offsets = row_offsets(counts)
         self.nbr = jj.to(torch.int32).contiguous()
         self.w = (lookup(edges) + lookup(jj * V + ii)).contiguous()
         self.p = (verts[ii] - verts[jj]).contiguous()
         self.verts = verts
         self.n_verts, self.n_faces, self.n_edges = V, F, int(edges.numel())
         self.max_valence = int(counts.max()) if V > 0 else 0
-
-    @property
-    def device(self):
-        return self.nbr.device
-
-    def to(self, device):
-        other = object.__new__(ArapBinding)
-        other.__dict__.update(self.__dict__)
-        for name in ("offsets", "nbr", "w", "p", "verts"):
-            setattr(other, name, getattr(self, name).to(device))
-        return other
 
 
 class _ArapEnergy(torch.autograd.Function):
@@ -140,7 +125,7 @@ class _ArapEnergy(torch.autograd.Function):
         energy = torch.zeros((T,), dtype=torch.float32, device=dev)
         if T > 0 and V > 0:
             nbytes = int(lib.gsr_sugar_arap_workspace_bytes(T, V))
-            ws = _workspace(nbytes, dev)
+            ws = workspace(nbytes, dev)
             _gsr._check(lib.gsr_sugar_arap_forward(*_ArapEnergy._args(vert_xyz, vert_rot, binding, form),
                                                    _gsr._ptr(energy), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
         return energy
@@ -154,7 +139,7 @@ class _ArapEnergy(torch.autograd.Function):
         if T == 0 or V == 0 or g_energy is None:
             return torch.zeros_like(vert_xyz), torch.zeros_like(vert_rot), None, None
         lib = _gsr.load_library()
-        (g,) = _ups((g_energy,), dev)
+        (g,) = ups((g_energy,), dev)
         dxyz, drot = torch.empty_like(vert_xyz), torch.empty_like(vert_rot)
         _gsr._check(lib.gsr_sugar_arap_backward(*_ArapEnergy._args(vert_xyz, vert_rot, ctx.binding, ctx.form),
                                                 _gsr._ptr(g), _gsr._ptr(dxyz), _gsr._ptr(drot), _gsr._stream(dev)))
@@ -177,18 +162,18 @@ def arap_energy(vert_xyz, vert_rot, binding):
     if not isinstance(binding, ArapBinding):
         raise ValueError("binding must be an ArapBinding")
     V = binding.n_verts
-    vert_xyz = _float_tensor(vert_xyz, "vert_xyz", (None, V, 3))
+    vert_xyz = float_tensor(vert_xyz, "vert_xyz", (None, V, 3))
     T = int(vert_xyz.shape[0])
     if isinstance(vert_rot, torch.Tensor) and vert_rot.dim() == 4:
-        vert_rot = _float_tensor(vert_rot, "vert_rot", (T, V, 3, 3))
+        vert_rot = float_tensor(vert_rot, "vert_rot", (T, V, 3, 3))
         form = ARAP_ROT_FORMS["matrix"]
     else:
         try:
-            vert_rot = _float_tensor(vert_rot, "vert_rot", (T, V, 4))
+            vert_rot = float_tensor(vert_rot, "vert_rot", (T, V, 4))
         except ValueError as e:
             raise ValueError(f"{e} (quaternions) or (T, V, 3, 3) (matrices)") from None
         form = ARAP_ROT_FORMS["quat"]
     if T * V >= 2 ** 31:
         raise ValueError("the batch is too large: T x V must stay below 2^31")
-    _on_gpu("arap_energy", vert_xyz, (("vert_rot", vert_rot), ("the binding", binding.nbr)))
-    return _ArapEnergy.apply(vert_xyz.contiguous(), _aligned(vert_rot), binding, form)
+    on_gpu("arap_energy", vert_xyz, (("vert_rot", vert_rot), ("the binding", binding.nbr)))
+    return _ArapEnergy.apply(vert_xyz.contiguous(), aligned(vert_rot), binding, form)

@@ -24,17 +24,15 @@ import ctypes
 import torch
 
 from diff_gaussian_rasterization import _C as _gsr
-from sugar_mesh import MeshBinding, _aligned
+from sugar_common import INT_DTYPES, Binding, aligned, float_tensor, incidence, on_gpu, ups, workspace
+from sugar_mesh import MeshBinding
 
 __all__ = ["SkinBinding", "skin_vertices", "timed_gaussians", "SKIN_MAX_K", "SKIN_METHODS"]
 
 SKIN_MAX_K = 32  # include/gsr.h GSR_SKIN_MAX_K
 SKIN_METHODS = {"dqs": 0, "lbs": 1}  # GSR_SKIN_DQS, GSR_SKIN_LBS
 
-_INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
-
-
-class SkinBinding:
+class SkinBinding(Binding):
     """What ``skin_vertices`` needs of a deformation graph besides the node positions, built once.
 
     nbr (V, K), any integer dtype, 1 <= K <= 32, every entry in [0, n_nodes) (checked here: one host
@@ -45,8 +43,10 @@ class SkinBinding:
     ``n_nodes``, ``n_neighbors``.  Works on CPU tensors too; ``to(device)`` moves it.
     """
 
+    _TENSORS = ("nbr", "w", "item_order", "node_offsets")
+
     def __init__(self, nbr, weights, n_nodes):
-        if not isinstance(nbr, torch.Tensor) or nbr.dtype not in _INT_DTYPES:
+        if not isinstance(nbr, torch.Tensor) or nbr.dtype not in INT_DTYPES:
             raise ValueError("nbr must be an integer tensor")
         if nbr.dim() != 2 or not 1 <= int(nbr.shape[1]) <= SKIN_MAX_K:
             raise ValueError(f"nbr must have shape (V, K) with 1 <= K <= {SKIN_MAX_K}, got {tuple(nbr.shape)}")
@@ -66,10 +66,7 @@ class SkinBinding:
             raise ValueError(f"nbr has entries outside [0, {n_nodes})")
         self.nbr = nbr.to(torch.int32).contiguous()
         self.w = weights.detach().to(torch.float32).contiguous()
-        self.item_order = torch.sort(flat, stable=True)[1].to(torch.int32).contiguous()
-        offsets = torch.zeros(n_nodes + 1, dtype=torch.int64, device=nbr.device)
-        offsets[1:] = torch.cumsum(torch.bincount(flat, minlength=n_nodes), 0)
-        self.node_offsets = offsets.to(torch.int32).contiguous()
+        self.item_order, self.node_offsets = incidence(flat, n_nodes)
         self.n_verts, self.n_nodes, self.n_neighbors = V, n_nodes, K
 
     @classmethod
@@ -95,44 +92,6 @@ class SkinBinding:
         nbr, dist = torch.cat(nbr), torch.cat(dist)
         return cls(nbr, dist / dist.sum(dim=-1, keepdim=True), P)
 
-    @property
-    def device(self):
-        return self.nbr.device
-
-    def to(self, device):
-        other = object.__new__(SkinBinding)
-        other.__dict__.update(self.__dict__)
-        for name in ("nbr", "w", "item_order", "node_offsets"):
-            setattr(other, name, getattr(self, name).to(device))
-        return other
-
-
-def _float_tensor(t, name, shape):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise ValueError(f"{name} must be a float32 tensor")
-    if t.dim() != len(shape) or any(s is not None and int(t.shape[i]) != s for i, s in enumerate(shape)):
-        want = tuple("T" if s is None else s for s in shape)
-        raise ValueError(f"{name} must have shape {want}, got {tuple(t.shape)}")
-    return t
-
-
-def _on_gpu(fn, first, others):
-    dev = first.device
-    if dev.type != "cuda":
-        raise ValueError(f"{fn} requires tensors on a ROCm GPU (device 'cuda'): there is no CPU path")
-    for name, t in others:
-        if t is not None and t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, expected {dev}")
-    return dev
-
-
-def _workspace(nbytes, dev):
-    return torch.empty((int(nbytes),), dtype=torch.uint8, device=dev)
-
-
-def _ups(grads, dev):
-    return [None if g is None else _aligned(_gsr._f32(g, "upstream gradient", dev)) for g in grads]
-
 
 class _SkinVertices(torch.autograd.Function):
     """(verts, node_trans, node_rots, node_scales) -> (vert_xyz, vert_rot, vert_scale)."""
@@ -150,7 +109,7 @@ class _SkinVertices(torch.autograd.Function):
         scale = None if node_scales is None else torch.empty((T, V, 3), **fopt)
         if T > 0 and V > 0:
             nbytes = int(lib.gsr_sugar_skin_workspace_bytes(T, V, P))
-            ws = _workspace(nbytes, dev)
+            ws = workspace(nbytes, dev)
             _gsr._check(lib.gsr_sugar_skin_forward(
                 T, V, P, K, method, _gsr._ptr(verts), _gsr._ptr(node_xyz), _gsr._ptr(node_trans),
                 _gsr._ptr(node_rots), _gsr._ptr(node_scales), _gsr._ptr(binding.nbr), _gsr._ptr(binding.w),
@@ -170,14 +129,14 @@ class _SkinVertices(torch.autograd.Function):
         if T == 0 or V == 0 or all(g is None for g in (g_xyz, g_rot, g_scale)):
             return (*zeros, None, None, None)
         lib = _gsr.load_library()
-        ups = _ups((g_xyz, g_rot, g_scale), dev)
+        g_ups = ups((g_xyz, g_rot, g_scale), dev)
         grads = [torch.empty_like(t) if t is not None else None for t in (verts, node_trans, node_rots, node_scales)]
         nbytes = int(lib.gsr_sugar_skin_workspace_bytes(T, V, P))
-        ws = _workspace(nbytes, dev)
+        ws = workspace(nbytes, dev)
         _gsr._check(lib.gsr_sugar_skin_backward(
             T, V, P, K, method, _gsr._ptr(verts), _gsr._ptr(node_xyz), _gsr._ptr(node_trans), _gsr._ptr(node_rots),
             _gsr._ptr(node_scales), _gsr._ptr(binding.nbr), _gsr._ptr(binding.w), _gsr._ptr(binding.item_order),
-            _gsr._ptr(binding.node_offsets), *(_gsr._ptr(g) for g in ups), *(_gsr._ptr(g) for g in grads),
+            _gsr._ptr(binding.node_offsets), *(_gsr._ptr(g) for g in g_ups), *(_gsr._ptr(g) for g in grads),
             _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
         return (*grads, None, None, None)
 
@@ -199,21 +158,21 @@ def skin_vertices(verts, node_xyz, node_trans, node_rots, binding, method="dqs",
     if method not in SKIN_METHODS:
         raise ValueError(f"method must be 'dqs' or 'lbs', got {method!r}")
     V, P = binding.n_verts, binding.n_nodes
-    verts = _float_tensor(verts, "verts", (V, 3))
-    node_xyz = _float_tensor(node_xyz, "node_xyz", (P, 3))
-    node_trans = _float_tensor(node_trans, "node_trans", (None, P, 3))
+    verts = float_tensor(verts, "verts", (V, 3))
+    node_xyz = float_tensor(node_xyz, "node_xyz", (P, 3))
+    node_trans = float_tensor(node_trans, "node_trans", (None, P, 3))
     T = int(node_trans.shape[0])
-    node_rots = _float_tensor(node_rots, "node_rots", (T, P, 4))
+    node_rots = float_tensor(node_rots, "node_rots", (T, P, 4))
     if node_scales is not None:
-        node_scales = _float_tensor(node_scales, "node_scales", (T, P, 3))
+        node_scales = float_tensor(node_scales, "node_scales", (T, P, 3))
     if T * max(V, P) >= 2 ** 31:
         raise ValueError("the batch is too large: T x V and T x P must stay below 2^31")
     if V > 0 and P == 0:
         raise ValueError("vertices without nodes")
-    dev = _on_gpu("skin_vertices", verts, (("node_xyz", node_xyz), ("node_trans", node_trans),
-                                           ("node_rots", node_rots), ("node_scales", node_scales),
-                                           ("the binding", binding.nbr)))
-    out = _SkinVertices.apply(verts.contiguous(), node_trans.contiguous(), _aligned(node_rots),
+    dev = on_gpu("skin_vertices", verts, (("node_xyz", node_xyz), ("node_trans", node_trans),
+                                          ("node_rots", node_rots), ("node_scales", node_scales),
+                                          ("the binding", binding.nbr)))
+    out = _SkinVertices.apply(verts.contiguous(), node_trans.contiguous(), aligned(node_rots),
                               None if node_scales is None else node_scales.contiguous(),
                               node_xyz.detach().contiguous(), binding, SKIN_METHODS[method])
     return out[0], out[1], out[2]
@@ -257,14 +216,14 @@ class _TimedGaussians(torch.autograd.Function):
         if T == 0 or F == 0 or all(g is None for g in (g_xyz, g_rotation, g_normals, g_scaling)):
             return (*(torch.zeros_like(t) if t is not None else None for t in inputs), None, None)
         lib = _gsr.load_library()
-        ups = _ups((g_xyz, g_rotation, g_normals, g_scaling), dev)
+        g_ups = ups((g_xyz, g_rotation, g_normals, g_scaling), dev)
         grads = [torch.empty_like(t) if t is not None else None for t in inputs]
         nbytes = int(lib.gsr_sugar_timed_workspace_bytes(T, F))
-        ws = _workspace(nbytes, dev)
+        ws = workspace(nbytes, dev)
         _gsr._check(lib.gsr_sugar_timed_backward(
             T, V, F, G, N, _gsr._ptr(vert_xyz), _gsr._ptr(vert_rot), _gsr._ptr(rotation0), _gsr._ptr(binding.faces),
             ctypes.c_void_p(binding.bary.data_ptr()), _gsr._ptr(vert_scale), _gsr._ptr(log_scales), ctx.thickness,
-            _gsr._ptr(binding.corner_order), _gsr._ptr(binding.vert_offsets), *(_gsr._ptr(g) for g in ups),
+            _gsr._ptr(binding.corner_order), _gsr._ptr(binding.vert_offsets), *(_gsr._ptr(g) for g in g_ups),
             *(_gsr._ptr(g) for g in grads), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
         return (*grads, None, None)
 
@@ -285,20 +244,20 @@ def timed_gaussians(vert_xyz, vert_rot, rotation0, binding, vert_scale=None, log
     if not isinstance(binding, MeshBinding):
         raise ValueError("binding must be a MeshBinding")
     V, N = binding.n_verts, binding.n_gaussians
-    vert_xyz = _float_tensor(vert_xyz, "vert_xyz", (None, V, 3))
+    vert_xyz = float_tensor(vert_xyz, "vert_xyz", (None, V, 3))
     T = int(vert_xyz.shape[0])
-    vert_rot = _float_tensor(vert_rot, "vert_rot", (T, V, 4))
+    vert_rot = float_tensor(vert_rot, "vert_rot", (T, V, 4))
     given = [x is not None for x in (vert_scale, log_scales, thickness)]
     if any(given) and not all(given):
         raise ValueError("vert_scale, log_scales and thickness are given together or not at all")
     try:
-        rotation0 = _float_tensor(rotation0, "rotation0", (N, 4))
+        rotation0 = float_tensor(rotation0, "rotation0", (N, 4))
         if all(given):
-            log_scales = _float_tensor(log_scales, "log_scales", (N, 2))
+            log_scales = float_tensor(log_scales, "log_scales", (N, 2))
     except ValueError as e:
         raise ValueError(f"{e} (N = F x G = {binding.n_faces} x {binding.n_per_face})") from None
     if all(given):
-        vert_scale = _float_tensor(vert_scale, "vert_scale", (T, V, 3))
+        vert_scale = float_tensor(vert_scale, "vert_scale", (T, V, 3))
         try:
             thickness = float(thickness)
         except (TypeError, ValueError):
@@ -307,10 +266,10 @@ def timed_gaussians(vert_xyz, vert_rot, rotation0, binding, vert_scale=None, log
         thickness = 0.0
     if T * max(V, N) >= 2 ** 31:
         raise ValueError("the batch is too large: T x N and T x V must stay below 2^31")
-    _on_gpu("timed_gaussians", vert_xyz, (("vert_rot", vert_rot), ("rotation0", rotation0),
-                                          ("vert_scale", vert_scale), ("log_scales", log_scales),
-                                          ("the binding", binding.faces)))
-    out = _TimedGaussians.apply(vert_xyz.contiguous(), _aligned(vert_rot), _aligned(rotation0),
+    on_gpu("timed_gaussians", vert_xyz, (("vert_rot", vert_rot), ("rotation0", rotation0),
+                                         ("vert_scale", vert_scale), ("log_scales", log_scales),
+                                         ("the binding", binding.faces)))
+    out = _TimedGaussians.apply(vert_xyz.contiguous(), aligned(vert_rot), aligned(rotation0),
                                 None if vert_scale is None else vert_scale.contiguous(),
-                                None if log_scales is None else _aligned(log_scales), binding, thickness)
+                                None if log_scales is None else aligned(log_scales), binding, thickness)
     return out[0], out[1], out[2], out[3]

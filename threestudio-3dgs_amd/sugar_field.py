@@ -33,6 +33,7 @@ import operator
 import torch
 
 from diff_gaussian_rasterization import _C as _gsr
+from sugar_common import float_tensor, on_gpu, ups, workspace
 
 __all__ = ["neighbor_density", "get_field_values", "neighbor_normal_loss", "smallest_axis",
            "sample_points_in_gaussians", "coarse_density_regulation", "FIELD_MAX_K"]
@@ -57,7 +58,7 @@ class _NeighborDensity(torch.autograd.Function):
         op = torch.empty((M, K), **fopt) if want_op else None
         if M > 0:
             nbytes = int(lib.gsr_sugar_field_workspace_bytes(0, K, N))
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            ws = workspace(nbytes, dev)
             _gsr._check(lib.gsr_sugar_field_forward(
                 M, K, N, R, _gsr._ptr(x), _gsr._ptr(nbr), _gsr._ptr(row), _gsr._ptr(centers), _gsr._ptr(inv_sr),
                 _gsr._ptr(strengths), _gsr._ptr(min_scale), density_factor, _gsr._ptr(density), _gsr._ptr(beta_avg),
@@ -76,26 +77,16 @@ class _NeighborDensity(torch.autograd.Function):
             grads = tuple(torch.zeros_like(t) for t in (x, centers, inv_sr, strengths, min_scale))
             return grads + (None, None, None, None)
         lib = _gsr.load_library()
-        g_density, g_beta, g_op = (None if g is None else _gsr._f32(g, "upstream gradient", dev)
-                                   for g in (g_density, g_beta, g_op))
+        g_density, g_beta, g_op = ups((g_density, g_beta, g_op), dev)
         dx, dc, dA, ds, dms = (torch.empty_like(t) for t in (x, centers, inv_sr, strengths, min_scale))
         nbytes = int(lib.gsr_sugar_field_workspace_bytes(M, K, N))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        ws = workspace(nbytes, dev)
         _gsr._check(lib.gsr_sugar_field_backward(
             M, K, N, R, _gsr._ptr(x), _gsr._ptr(nbr), _gsr._ptr(row), _gsr._ptr(centers), _gsr._ptr(inv_sr),
             _gsr._ptr(strengths), _gsr._ptr(min_scale), ctx.density_factor, _gsr._ptr(g_density), _gsr._ptr(g_beta),
             _gsr._ptr(g_op), _gsr._ptr(dx), _gsr._ptr(dc), _gsr._ptr(dA), _gsr._ptr(ds), _gsr._ptr(dms),
             _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
         return dx, dc, dA, ds, dms, None, None, None, None
-
-
-def _float_tensor(t, name, shape):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise ValueError(f"{name} must be a float32 tensor")
-    if t.dim() != len(shape) or any(s is not None and int(t.shape[i]) != s for i, s in enumerate(shape)):
-        want = ", ".join("*" if s is None else str(s) for s in shape)
-        raise ValueError(f"{name} must have shape ({want}), got {tuple(t.shape)}")
-    return t
 
 
 def _index_tensor(t, name, dims):
@@ -138,26 +129,23 @@ def neighbor_density(x, centers, inv_scaled_rotation, strengths, min_scaling, *,
     contributes nothing; a ``gaussian_idx`` outside the table gives zeros.  Gradients flow to all five float inputs,
     bitwise reproducible; no double backward.
     """
-    x = _float_tensor(x, "x", (None, 3))
+    x = float_tensor(x, "x", (None, 3))
     M = int(x.shape[0])
-    centers = _float_tensor(centers, "centers", (None, 3))
+    centers = float_tensor(centers, "centers", (None, 3))
     N = int(centers.shape[0])
-    inv_sr = _float_tensor(inv_scaled_rotation, "inv_scaled_rotation", (N, 3, 3))
+    inv_sr = float_tensor(inv_scaled_rotation, "inv_scaled_rotation", (N, 3, 3))
     if isinstance(strengths, torch.Tensor) and strengths.dim() == 2:
-        strengths = _float_tensor(strengths, "strengths", (N, 1)).reshape(N)
-    strengths = _float_tensor(strengths, "strengths", (N,))
-    min_scaling = _float_tensor(min_scaling, "min_scaling", (N,))
+        strengths = float_tensor(strengths, "strengths", (N, 1)).reshape(N)
+    strengths = float_tensor(strengths, "strengths", (N,))
+    min_scaling = float_tensor(min_scaling, "min_scaling", (N,))
     nbr, row = _neighbour_table(M, knn_idx, gaussian_idx, closest_gaussians_idx)
     try:
         density_factor = float(density_factor)
     except (TypeError, ValueError):
         raise ValueError("density_factor must be a number") from None
-    dev = x.device
-    _gsr._require_gpu(dev)
-    for name, t in (("centers", centers), ("inv_scaled_rotation", inv_sr), ("strengths", strengths),
-                    ("min_scaling", min_scaling), ("neighbour indices", nbr), ("gaussian_idx", row)):
-        if t is not None and t.device != dev:
-            raise _gsr.GSRError(f"{name} is on {t.device}, expected {dev}")
+    on_gpu("neighbor_density", x, (("centers", centers), ("inv_scaled_rotation", inv_sr), ("strengths", strengths),
+                                   ("min_scaling", min_scaling), ("neighbour indices", nbr), ("gaussian_idx", row)),
+           error=_gsr.GSRError)
     return _NeighborDensity.apply(x.contiguous(), centers.contiguous(), inv_sr.contiguous(), strengths.contiguous(),
                                   min_scaling.contiguous(), nbr.contiguous(),
                                   None if row is None else row.contiguous(), density_factor,
@@ -180,7 +168,7 @@ def get_field_values(x, *, points, inv_scaled_rotation, strengths, scaling, knn_
     need_beta = return_sdf or return_beta
     if need_beta and beta_mode == "learnable" and not isinstance(log_beta, torch.Tensor):
         raise ValueError("beta_mode='learnable' needs log_beta")
-    scaling = _float_tensor(scaling, "scaling", (None, 3))
+    scaling = float_tensor(scaling, "scaling", (None, 3))
     min_scaling = scaling.min(dim=-1)[0]
     weighted = need_beta and beta_mode == "weighted_average"
     density, beta_avg, opacities = neighbor_density(
@@ -231,7 +219,7 @@ class _NeighborNormalLoss(torch.autograd.Function):
         rec = torch.empty((M, 4), **fopt) if ctx.needs_input_grad[2] else None  # (r, Wc): all the backward keeps
         if M > 0:
             nbytes = int(lib.gsr_sugar_normal_workspace_bytes(0, K, N))
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            ws = workspace(nbytes, dev)
             _gsr._check(lib.gsr_sugar_normal_forward(
                 M, K, N, R, _gsr._ptr(x), _gsr._ptr(own), _gsr._ptr(nbr), int(per_sample), _gsr._ptr(centers),
                 _gsr._ptr(normals), _gsr._ptr(min_scale), _gsr._ptr(op), _gsr._ptr(loss), _gsr._ptr(rec),
@@ -251,10 +239,10 @@ class _NeighborNormalLoss(torch.autograd.Function):
         if M == 0 or N == 0:
             return (None, None, torch.zeros_like(normals)) + (None,) * 5
         lib = _gsr.load_library()
-        g_loss = _gsr._f32(g_loss, "upstream gradient", dev)
+        (g_loss,) = ups((g_loss,), dev)
         dnormals = torch.empty_like(normals)
         nbytes = int(lib.gsr_sugar_normal_workspace_bytes(M, K, N))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        ws = workspace(nbytes, dev)
         _gsr._check(lib.gsr_sugar_normal_backward(
             M, K, N, R, _gsr._ptr(x), _gsr._ptr(own), _gsr._ptr(nbr), int(ctx.per_sample), _gsr._ptr(centers),
             _gsr._ptr(normals), _gsr._ptr(min_scale), _gsr._ptr(op), _gsr._ptr(rec), _gsr._ptr(g_loss),
@@ -281,25 +269,22 @@ def neighbor_normal_loss(x, centers, normals, min_scaling, opacities, *, gaussia
     """
     if not gradient_through_normal_only:
         raise NotImplementedError("neighbor_normal_loss: gradient_through_normal_only=False is not supported")
-    x = _float_tensor(x, "x", (None, 3))
+    x = float_tensor(x, "x", (None, 3))
     M = int(x.shape[0])
-    centers = _float_tensor(centers, "centers", (None, 3))
+    centers = float_tensor(centers, "centers", (None, 3))
     N = int(centers.shape[0])
-    normals = _float_tensor(normals, "normals", (N, 3))
-    min_scaling = _float_tensor(min_scaling, "min_scaling", (N,))
+    normals = float_tensor(normals, "normals", (N, 3))
+    min_scaling = float_tensor(min_scaling, "min_scaling", (N,))
     own = _index_tensor(gaussian_idx, "gaussian_idx", 1)
     if int(own.shape[0]) != M:
         raise ValueError(f"gaussian_idx must have one entry per sample ({M}), got {int(own.shape[0])}")
     if (knn_idx is None) == (closest_gaussians_idx is None):
         raise ValueError("give either knn_idx or closest_gaussians_idx (one of the two forms)")
     nbr, _ = _neighbour_table(M, knn_idx, None if knn_idx is None else own, closest_gaussians_idx)
-    opacities = _float_tensor(opacities, "opacities", (M, int(nbr.shape[1])))
-    dev = x.device
-    _gsr._require_gpu(dev)
-    for name, t in (("centers", centers), ("normals", normals), ("min_scaling", min_scaling),
-                    ("opacities", opacities), ("neighbour indices", nbr), ("gaussian_idx", own)):
-        if t.device != dev:
-            raise _gsr.GSRError(f"{name} is on {t.device}, expected {dev}")
+    opacities = float_tensor(opacities, "opacities", (M, int(nbr.shape[1])))
+    on_gpu("neighbor_normal_loss", x, (("centers", centers), ("normals", normals), ("min_scaling", min_scaling),
+                                       ("opacities", opacities), ("neighbour indices", nbr), ("gaussian_idx", own)),
+           error=_gsr.GSRError)
     return _NeighborNormalLoss.apply(x.contiguous(), centers.contiguous(), normals.contiguous(),
                                      min_scaling.contiguous(), opacities.contiguous(), own.contiguous(),
                                      nbr.contiguous(), knn_idx is None)
@@ -332,8 +317,8 @@ def smallest_axis(quaternions, scaling):
     """``get_smallest_axis`` (utils/sugar_utils.py:355-372), the normals of ``get_normals()`` for Gaussians not bound
     to a mesh: the column of each rotation matrix at the argmin of its scales, (N, 3).  quaternions (N, 4) are
     (w, x, y, z) and are normalised here; scaling (N, 3)."""
-    quaternions = _float_tensor(quaternions, "quaternions", (None, 4))
-    scaling = _float_tensor(scaling, "scaling", (int(quaternions.shape[0]), 3))
+    quaternions = float_tensor(quaternions, "quaternions", (None, 4))
+    scaling = float_tensor(scaling, "scaling", (int(quaternions.shape[0]), 3))
     idx = scaling.min(dim=-1)[1][..., None, None].expand(-1, 3, -1)
     return _quaternion_to_matrix(quaternions).gather(2, idx).squeeze(dim=2)
 
@@ -348,10 +333,10 @@ def sample_points_in_gaussians(points, quaternions, scaling, num_samples, sampli
     (masked) list is drawn with a weight proportional to the summed area of Gaussians 0..n, so even the "uniform"
     setting (neither proportional flag) favours high indices linearly.  quaternions are normalised here;
     ``generator`` seeds both the draw of the indices and the Gaussian noise (None: the default generator)."""
-    points = _float_tensor(points, "points", (None, 3))
+    points = float_tensor(points, "points", (None, 3))
     n = int(points.shape[0])
-    quaternions = _float_tensor(quaternions, "quaternions", (n, 4))
-    all_scaling = _float_tensor(scaling, "scaling", (n, 3))
+    quaternions = float_tensor(quaternions, "quaternions", (n, 4))
+    all_scaling = float_tensor(scaling, "scaling", (n, 3))
     scaling = all_scaling if mask is None else all_scaling[mask]
     if probabilities_proportional_to_volume:
         areas = scaling[..., 0] * scaling[..., 1] * scaling[..., 2]

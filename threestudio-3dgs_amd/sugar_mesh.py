@@ -21,6 +21,7 @@ import math
 import torch
 
 from diff_gaussian_rasterization import _C as _gsr
+from sugar_common import INT_DTYPES, Binding, aligned, float_tensor, incidence, on_gpu, ups, workspace
 
 __all__ = ["MeshBinding", "bound_gaussians", "initial_log_scales", "REFERENCE_BARY", "REFERENCE_CIRCLE_RADIUS",
            "MESH_MAX_G"]
@@ -43,10 +44,7 @@ REFERENCE_CIRCLE_RADIUS = {
     6: 1. / (4. + 2. * math.sqrt(3.)),
 }
 
-_INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
-
-
-class MeshBinding:
+class MeshBinding(Binding):
     """What ``bound_gaussians`` needs of a mesh besides its vertices, built once.
 
     faces (F, 3), any integer dtype, every entry in [0, n_verts) (checked here: one host synchronisation);
@@ -58,8 +56,10 @@ class MeshBinding:
     Works on CPU tensors too; ``to(device)`` moves the index tensors.
     """
 
+    _TENSORS = ("faces", "corner_order", "vert_offsets")
+
     def __init__(self, faces, n_verts, bary, circle_radius=None):
-        if not isinstance(faces, torch.Tensor) or faces.dtype not in _INT_DTYPES:
+        if not isinstance(faces, torch.Tensor) or faces.dtype not in INT_DTYPES:
             raise ValueError("faces must be an integer tensor")
         if faces.dim() != 2 or int(faces.shape[1]) != 3:
             raise ValueError(f"faces must have shape (*, 3), got {tuple(faces.shape)}")
@@ -78,11 +78,7 @@ class MeshBinding:
         if F > 0 and (int(flat.min()) < 0 or int(flat.max()) >= n_verts):
             raise ValueError(f"faces has entries outside [0, {n_verts})")
         self.faces = faces.to(torch.int32).contiguous()
-        order = torch.sort(flat, stable=True)[1]
-        self.corner_order = order.to(torch.int32).contiguous()
-        offsets = torch.zeros(n_verts + 1, dtype=torch.int64, device=faces.device)
-        offsets[1:] = torch.cumsum(torch.bincount(flat, minlength=n_verts), 0)
-        self.vert_offsets = offsets.to(torch.int32).contiguous()
+        self.corner_order, self.vert_offsets = incidence(flat, n_verts)
         self.bary = bary
         self.n_verts, self.n_faces, self.n_per_face = n_verts, F, int(bary.shape[0])
         self.n_gaussians = F * self.n_per_face
@@ -96,23 +92,12 @@ class MeshBinding:
             raise ValueError(f"the reference places 1, 3, 4 or 6 Gaussians per triangle, not {G!r}")
         return cls(faces, n_verts, REFERENCE_BARY[G], REFERENCE_CIRCLE_RADIUS[G])
 
-    @property
-    def device(self):
-        return self.faces.device
-
-    def to(self, device):
-        other = object.__new__(MeshBinding)
-        other.__dict__.update(self.__dict__)
-        for name in ("faces", "corner_order", "vert_offsets"):
-            setattr(other, name, getattr(self, name).to(device))
-        return other
-
 
 def initial_log_scales(verts, binding, circle_radius=None):
     """``initialize_learnable_radiuses`` (geometry/sugar.py:311-327): the initial ``_scales`` (N, 2) of the bound
     Gaussians, log of max(shortest side of the face x circle radius, 1e-7), the same for a face's G Gaussians and for
     both in-plane axes.  Init only, plain torch (CPU or GPU)."""
-    verts = _float_tensor(verts, "verts", (binding.n_verts, 3))
+    verts = float_tensor(verts, "verts", (binding.n_verts, 3))
     radius = binding.circle_radius if circle_radius is None else circle_radius
     if radius is None:
         raise ValueError("this binding has no circle radius: give circle_radius")
@@ -120,20 +105,6 @@ def initial_log_scales(verts, binding, circle_radius=None):
     scales = (fv - fv[:, [1, 2, 0]]).norm(dim=-1).min(dim=-1)[0] * radius
     scales = scales.clamp_min(0.0000001).reshape(-1, 1, 1).expand(-1, binding.n_per_face, 2)
     return torch.log(scales).reshape(-1, 2).contiguous()
-
-
-def _float_tensor(t, name, shape):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise ValueError(f"{name} must be a float32 tensor")
-    if t.dim() != len(shape) or any(int(t.shape[i]) != s for i, s in enumerate(shape)):
-        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-    return t
-
-
-def _aligned(t, alignment=16):
-    """t contiguous and aligned (a view at an odd storage offset is copied)."""
-    t = t.contiguous()
-    return t if t.data_ptr() % alignment == 0 else t.clone()
 
 
 def _bary_ptr(binding):
@@ -171,15 +142,14 @@ class _BoundGaussians(torch.autograd.Function):
         if F == 0 or all(g is None for g in (g_xyz, g_scaling, g_rotation, g_normals)):
             return torch.zeros_like(verts), torch.zeros_like(cplx), torch.zeros_like(log_scales), None, None
         lib = _gsr.load_library()
-        ups = [None if g is None else _aligned(_gsr._f32(g, "upstream gradient", dev))
-               for g in (g_xyz, g_scaling, g_rotation, g_normals)]
+        grads = ups((g_xyz, g_scaling, g_rotation, g_normals), dev)
         dverts, dcplx, dls = torch.empty_like(verts), torch.empty_like(cplx), torch.empty_like(log_scales)
         nbytes = int(lib.gsr_sugar_mesh_workspace_bytes(F, V))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        ws = workspace(nbytes, dev)
         _gsr._check(lib.gsr_sugar_mesh_backward(
             V, F, G, N, _gsr._ptr(verts), _gsr._ptr(binding.faces), _bary_ptr(binding), _gsr._ptr(cplx),
             _gsr._ptr(log_scales), _gsr._ptr(binding.corner_order), _gsr._ptr(binding.vert_offsets),
-            *(_gsr._ptr(g) for g in ups), _gsr._ptr(dverts), _gsr._ptr(dcplx), _gsr._ptr(dls), _gsr._ptr(ws), nbytes,
+            *(_gsr._ptr(g) for g in grads), _gsr._ptr(dverts), _gsr._ptr(dcplx), _gsr._ptr(dls), _gsr._ptr(ws), nbytes,
             _gsr._stream(dev)))
         return dverts, dcplx, dls, None, None
 
@@ -199,21 +169,17 @@ def bound_gaussians(verts, complex_numbers, log_scales, binding, thickness):
     """
     if not isinstance(binding, MeshBinding):
         raise ValueError("binding must be a MeshBinding")
-    verts = _float_tensor(verts, "verts", (binding.n_verts, 3))
+    verts = float_tensor(verts, "verts", (binding.n_verts, 3))
     N = binding.n_gaussians
     try:
-        cplx = _float_tensor(complex_numbers, "complex_numbers", (N, 2))
-        log_scales = _float_tensor(log_scales, "log_scales", (N, 2))
+        cplx = float_tensor(complex_numbers, "complex_numbers", (N, 2))
+        log_scales = float_tensor(log_scales, "log_scales", (N, 2))
     except ValueError as e:
         raise ValueError(f"{e} (N = F x G = {binding.n_faces} x {binding.n_per_face})") from None
     try:
         thickness = float(thickness)
     except (TypeError, ValueError):
         raise ValueError("thickness must be a number") from None
-    dev = verts.device
-    if dev.type != "cuda":
-        raise ValueError("bound_gaussians requires tensors on a ROCm GPU (device 'cuda'): there is no CPU path")
-    for name, t in (("complex_numbers", cplx), ("log_scales", log_scales), ("the binding", binding.faces)):
-        if t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, expected {dev}")
-    return _BoundGaussians.apply(verts.contiguous(), _aligned(cplx), _aligned(log_scales), binding, thickness)
+    on_gpu("bound_gaussians", verts, (("complex_numbers", cplx), ("log_scales", log_scales),
+                                      ("the binding", binding.faces)))
+    return _BoundGaussians.apply(verts.contiguous(), aligned(cplx), aligned(log_scales), binding, thickness)
