@@ -78,7 +78,9 @@ const char* gsr_version(void);
  *      gsr_sugar_timed_workspace_bytes / gsr_sugar_timed_forward / gsr_sugar_timed_backward (dynamic SuGaR: the
  *      deformation-graph skinning of the vertices and the Gaussians of the deformed mesh, for all frames of a batch);
  *      gsr_sugar_arap_workspace_bytes / gsr_sugar_arap_forward / gsr_sugar_arap_backward (dynamic SuGaR: the
- *      as-rigid-as-possible energy of the deformed vertices, for all frames of a batch).
+ *      as-rigid-as-possible energy of the deformed vertices, for all frames of a batch);
+ *      gsr_sugar_spline_workspace_bytes / gsr_sugar_spline_forward / gsr_sugar_spline_backward (dynamic SuGaR: the
+ *      B-spline from the control knots to the timed node attributes).
  */
 #define GSR_ABI_VERSION 8
 int gsr_abi_version(void);
@@ -732,6 +734,52 @@ int gsr_sugar_arap_forward(int T, int V, int E, int rot_form, const float* verts
 int gsr_sugar_arap_backward(int T, int V, int E, int rot_form, const float* verts, const int* offsets, const int* nbr,
                             const float* w, const float* vert_xyz, const float* vert_rot, const float* dL_denergy,
                             float* dL_dvert_xyz, float* dL_dvert_rot, void* stream);
+
+/*
+ * gsr_sugar_spline_*: the B-spline that turns the control knots of the deformation network into the timed node (or
+ * vertex) attributes (Spline.forward, geometry/spline_utils.py:195-332, as get_timed_dg_attributes and
+ * get_timed_vertex_attributes call it, dynamic_sugar.py:425-435, 488-494), for all T timestamps of a call.  P points,
+ * n_knots knots, degree 1 or 3 (n_knots >= degree + 1); T P and n_knots P < 2^31.
+ *   timestamps (T,);  knots_xyz (n_knots,P,3);  knots_rot (n_knots,P,4) xyzw, non-zero, any norm, 16-byte aligned;
+ *   knots_scale (n_knots,P,3) or NULL: frame-major, as _get_timed_dg_attributes_wo_spline returns them (the
+ *   reference's set_data tensors are their permute(1, 0, 2)).
+ *   start_time, interval (> 0): the grid, knot k at start_time + k interval;  t_lo, t_hi: the clamp bounds (the
+ *   reference's t_lower_bound + 1e-6 and t_upper_bound - 1e-6 as it forms them in fp32).
+ * The segment of a timestamp, in fp32 as the reference takes it (a discrete decision):
+ *   ts = min(max(t, t_lo), t_hi);  nt = (ts - start_time) / interval (correctly rounded);  i = (int) floor(nt);
+ *   u = nt - (float) i;  degree 3: i -= 1;  then i is clamped to [0, n_knots - degree - 1], so that no timestamp (NaN
+ *   included: its outputs are unspecified) reads outside the knots.
+ * With k_j = knots[i + j][p], u taken to fp64, the sums in ascending j:
+ *   degree 3, xyz and scale:  sum_j c_j k_j,  c = (1/6 - u/2 + u^2/2 - u^3/6,  4/6 - u^2 + u^3/2,
+ *                             1/6 + u/2 + u^2/2 - u^3/2,  u^3/6)
+ *   degree 3, rot:  r_j = Log(conj(q_j) (x) q_j+1), j = 0, 1, 2;  b = (5/6 + u/2 - u^2/2 + u^3/6,
+ *                   1/6 + u/2 + u^2/2 - u^3/3,  u^3/6);  rot = q_0 (x) Exp(b_0 r_0) (x) Exp(b_1 r_1) (x) Exp(b_2 r_2)
+ *                   (no normalisation and no sign fix, as the reference: |rot| = |q_0|)
+ *   degree 1, xyz and scale:  (1 - u) k_0 + u k_1;   rot = Exp((1 - u) Log(q_0) + u Log(q_1))
+ * Log, Exp and (x) as above.  Outputs xyz (T,P,3), rot (T,P,4) xyzw 16-byte aligned, scale (T,P,3) (required iff
+ * knots_scale is given): the node_trans, node_rots, node_scales of gsr_sugar_skin_*, or with P = V the vert_xyz,
+ * vert_rot, vert_scale of gsr_sugar_timed_*.
+ * Backward: the exact derivative to the knots (none to the timestamps).  dL_dxyz (T,P,3), dL_drot (T,P,4) 16-byte
+ * aligned, dL_dscale (T,P,3): any may be NULL (zero).  Writes in full dL_dknots_xyz (n_knots,P,3), dL_dknots_rot
+ * (n_knots,P,4) 16-byte aligned and, iff knots_scale is given, dL_dknots_scale (n_knots,P,3); a knot that no
+ * timestamp's segment covers gets exactly 0.
+ * Sum order (no atomics; two calls give the same bits): per (knot, p) the rows of the covering timestamps in ascending
+ * t, from 0.  Precision: fp64 arithmetic from the fp32 inputs and the fp32 u; outputs and gradients are rounded to fp32
+ * once (the rows between the backward's two kernels are fp64).
+ * workspace (backward only): gsr_sugar_spline_workspace_bytes(T, P, degree) bytes of device memory (256-B aligned):
+ * 80 (degree + 1) T P bytes, the fp64 rows (10 per timestamp, point and knot of its segment).  The forward is one
+ * launch, the backward two, on `stream`; the library allocates nothing.  T = 0 or P = 0 launches nothing and writes
+ * nothing (the caller zeroes the gradients).
+ */
+size_t gsr_sugar_spline_workspace_bytes(int T, int P, int degree);
+int gsr_sugar_spline_forward(int T, int P, int n_knots, int degree, float start_time, float interval, float t_lo,
+                             float t_hi, const float* timestamps, const float* knots_xyz, const float* knots_rot,
+                             const float* knots_scale, float* xyz, float* rot, float* scale, void* stream);
+int gsr_sugar_spline_backward(int T, int P, int n_knots, int degree, float start_time, float interval, float t_lo,
+                              float t_hi, const float* timestamps, const float* knots_xyz, const float* knots_rot,
+                              const float* knots_scale, const float* dL_dxyz, const float* dL_drot,
+                              const float* dL_dscale, float* dL_dknots_xyz, float* dL_dknots_rot,
+                              float* dL_dknots_scale, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * The view-segmented stable LSD radix sort that every sort of this library runs (the depth sort, the tile sort and

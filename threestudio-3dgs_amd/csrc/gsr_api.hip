@@ -860,6 +860,71 @@ int gsr_sugar_arap_backward(int T, int V, int E, int rot_form, const float* vert
   return last_launch();
 }
 
+// ---- the B-spline of the timed node attributes (gsr_spline.hip) -------------------------------------
+static int spline_check(int T, int P, int n_knots, int degree, float start_time, float interval, float t_lo,
+                        float t_hi, const float* timestamps, const float* knots_xyz, const float* knots_rot,
+                        const float* knots_scale, SplineCall& c) {
+  if (degree != 1 && degree != 3) return fail(GSR_EINVAL, "%s", "degree must be 1 or 3");
+  if (n_knots < degree + 1) return fail(GSR_EINVAL, "%s", "n_knots must be at least degree + 1");
+  if (T < 0 || P < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if (!(interval > 0.0f)) return fail(GSR_EINVAL, "%s", "interval must be positive");
+  if (!below_2_31(T, P) || !below_2_31(n_knots, P))
+    return fail(GSR_EINVAL, "%s", "T x P and n_knots x P must stay below 2^31");
+  if (T > 0 && P > 0 && (timestamps == nullptr || knots_xyz == nullptr || knots_rot == nullptr))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (((uintptr_t)knots_rot & 15u) != 0) return fail(GSR_EINVAL, "%s", "knots_rot must be 16-byte aligned");
+  c = SplineCall{T, P, n_knots, degree, start_time, interval, t_lo, t_hi, timestamps, knots_xyz, knots_rot,
+                 knots_scale};
+  return GSR_OK;
+}
+
+size_t gsr_sugar_spline_workspace_bytes(int T, int P, int degree) {
+  return spline_workspace_bytes(T < 0 ? 0 : T, P < 0 ? 0 : P, degree);
+}
+
+int gsr_sugar_spline_forward(int T, int P, int n_knots, int degree, float start_time, float interval, float t_lo,
+                             float t_hi, const float* timestamps, const float* knots_xyz, const float* knots_rot,
+                             const float* knots_scale, float* xyz, float* rot, float* scale, void* stream) {
+  SplineCall c;
+  if (spline_check(T, P, n_knots, degree, start_time, interval, t_lo, t_hi, timestamps, knots_xyz, knots_rot,
+                   knots_scale, c) != GSR_OK)
+    return GSR_EINVAL;
+  if (T == 0 || P == 0) {  // nothing to launch, no device touched
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (xyz == nullptr || rot == nullptr || (knots_scale != nullptr && scale == nullptr))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (((uintptr_t)rot & 15u) != 0) return fail(GSR_EINVAL, "%s", "rot must be 16-byte aligned");
+  launch_spline_forward(c, xyz, rot, scale, (hipStream_t)stream);
+  return last_launch();
+}
+
+int gsr_sugar_spline_backward(int T, int P, int n_knots, int degree, float start_time, float interval, float t_lo,
+                              float t_hi, const float* timestamps, const float* knots_xyz, const float* knots_rot,
+                              const float* knots_scale, const float* dL_dxyz, const float* dL_drot,
+                              const float* dL_dscale, float* dL_dknots_xyz, float* dL_dknots_rot,
+                              float* dL_dknots_scale, void* workspace, size_t workspace_bytes, void* stream) {
+  SplineCall c;
+  if (spline_check(T, P, n_knots, degree, start_time, interval, t_lo, t_hi, timestamps, knots_xyz, knots_rot,
+                   knots_scale, c) != GSR_OK)
+    return GSR_EINVAL;
+  if (T == 0 || P == 0) {
+    g_err[0] = 0;
+    return GSR_OK;
+  }
+  if (dL_dknots_xyz == nullptr || dL_dknots_rot == nullptr || workspace == nullptr ||
+      (knots_scale != nullptr && dL_dknots_scale == nullptr))
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if ((((uintptr_t)dL_drot | (uintptr_t)dL_dknots_rot) & 15u) != 0)
+    return fail(GSR_EINVAL, "%s", "dL_drot and dL_dknots_rot must be 16-byte aligned");
+  if (((uintptr_t)workspace & 7u) != 0) return fail(GSR_EINVAL, "%s", "workspace must be 8-byte aligned");
+  if (workspace_bytes < spline_workspace_bytes(T, P, degree)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_spline_backward(c, dL_dxyz, dL_drot, dL_dscale, dL_dknots_xyz, dL_dknots_rot, dL_dknots_scale, workspace,
+                         (hipStream_t)stream);
+  return last_launch();
+}
+
 // ---- the view-segmented radix sort (tests: every sort of the library runs seg_sort) -----------------
 struct SortWork {
   uint32_t *keys2, *vals2, *counts, *totals;

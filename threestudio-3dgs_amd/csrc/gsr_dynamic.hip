@@ -40,9 +40,6 @@ namespace gsr {
 
 GSR_HD Q4 rec_q(const double* r) { return q4(d3(r[0], r[1], r[2]), r[3]); }
 GSR_HD D3 rec_d3(const double* r) { return d3(r[0], r[1], r[2]); }
-GSR_HD void store4(float* p, Q4 q) {  // (x, y, z, w)
-  *(float4*)p = make_float4((float)q.v.x, (float)q.v.y, (float)q.v.z, (float)q.w);
-}
 GSR_HD Q4 load_q_row(const float* p) { return q4(d3((double)p[0], (double)p[1], (double)p[2]), (double)p[3]); }
 GSR_HD Q4 load_wxyz(const float* p) {
   const float4 q = *(const float4*)p;
@@ -51,7 +48,6 @@ GSR_HD Q4 load_wxyz(const float* p) {
 GSR_HD void store_wxyz(float* p, Q4 q) {
   *(float4*)p = make_float4((float)q.w, (float)q.v.x, (float)q.v.y, (float)q.v.z);
 }
-GSR_HD Q4 qzero() { return q4(d3(0.0, 0.0, 0.0), 0.0); }
 
 // ---- skinning ---------------------------------------------------------------------------------------------------
 GSR_HD void skin_node_record(const SkinCall& a, long long i, double* nodes) {  // i = t P + node

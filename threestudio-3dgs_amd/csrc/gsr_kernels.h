@@ -342,6 +342,19 @@ struct ArapCall {
 size_t arap_workspace_bytes(int T, int V);
 void launch_arap_forward(const ArapCall& c, float* energy, void* workspace, hipStream_t stream);
 void launch_arap_backward(const ArapCall& c, const float* g_energy, float* dxyz, float* drot, hipStream_t stream);
+// The B-spline of the timed node attributes (include/gsr.h gsr_sugar_spline_*) — gsr_spline.hip.  T timestamps, P
+// points, n_knots frame-major knots of degree 1 or 3; knots_scale may be null.  The backward's workspace holds the
+// (T, degree + 1, 10, P) fp64 gradient rows.
+struct SplineCall {
+  int T, P, n_knots, degree;
+  float start, interval, lo, hi;  // the grid and the clamp bounds, fp32
+  const float *timestamps, *knots_xyz, *knots_rot, *knots_scale;
+};
+size_t spline_workspace_bytes(int T, int P, int degree);
+void launch_spline_forward(const SplineCall& c, float* xyz, float* rot, float* scale, hipStream_t stream);
+void launch_spline_backward(const SplineCall& c, const float* g_xyz, const float* g_rot, const float* g_scale,
+                            float* dknots_xyz, float* dknots_rot, float* dknots_scale, void* workspace,
+                            hipStream_t stream);
 void launch_gauss_backward(const GaussBackwardArgs& a, ViewGradArgs va, const AccumArgs& b, hipStream_t stream);
 
 }  // namespace gsr

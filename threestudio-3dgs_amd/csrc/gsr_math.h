@@ -213,10 +213,17 @@ GSR_HD Q4 conj(Q4 a) { return q4(-1.0 * a.v, a.w); }
 GSR_HD Q4 qmul(Q4 a, Q4 b) {
   return q4(a.w * b.v + b.w * a.v + cross(a.v, b.v), a.w * b.w - dot(a.v, b.v));
 }
+// the adjoints of c = a (x) b, given the gradient g to c (any norms)
+GSR_HD Q4 qmul_grad_a(Q4 g, Q4 b) { return qmul(g, conj(b)); }
+GSR_HD Q4 qmul_grad_b(Q4 a, Q4 g) { return qmul(conj(a), g); }
 GSR_HD Q4 load_xyzw(const float* p) {
   const float4 q = *(const float4*)p;
   return q4(d3((double)q.x, (double)q.y, (double)q.z), (double)q.w);
 }
+GSR_HD void store4(float* p, Q4 q) {  // (x, y, z, w)
+  *(float4*)p = make_float4((float)q.v.x, (float)q.v.y, (float)q.v.z, (float)q.w);
+}
+GSR_HD Q4 qzero() { return q4(d3(0.0, 0.0, 0.0), 0.0); }
 
 // below these (|v|^2 / w^2 for Log, |phi|^2 for Exp) the series are taken: their first dropped terms are < 1e-17
 #define GSR_LOG_SERIES 1e-8

@@ -121,6 +121,9 @@ SIGNATURES = {
     "gsr_sugar_arap_workspace_bytes": (_sz, [_i, _i]),
     "gsr_sugar_arap_forward": (_i, [_i] * 4 + [_vp] * 6 + [_vp] + [_vp, _sz, _vp]),
     "gsr_sugar_arap_backward": (_i, [_i] * 4 + [_vp] * 6 + [_vp] + [_vp] * 2 + [_vp]),
+    "gsr_sugar_spline_workspace_bytes": (_sz, [_i, _i, _i]),
+    "gsr_sugar_spline_forward": (_i, [_i] * 4 + [_f] * 4 + [_vp] * 4 + [_vp] * 3 + [_vp]),
+    "gsr_sugar_spline_backward": (_i, [_i] * 4 + [_f] * 4 + [_vp] * 4 + [_vp] * 3 + [_vp] * 3 + [_vp, _sz, _vp]),
     "gsr_set_geom_bytes": (_sz, [_i, _i]),
     "gsr_set_binning_bytes": (_sz, [_i, _i, ctypes.POINTER(_i), _i, _i]),
     "gsr_set_image_bytes": (_sz, [_i, _i, _ip, _i, _i, _i]),

@@ -1,5 +1,5 @@
-"""What the fused SuGaR stages (sugar_field, sugar_mesh, sugar_dynamic, sugar_arap) share on the Python side: argument
-checks, the buffers of a call and the incidence tables of the bindings.  No public API."""
+"""What the fused SuGaR stages (sugar_field, sugar_mesh, sugar_dynamic, sugar_arap, sugar_spline) share on the Python
+side: argument checks, the buffers of a call and the incidence tables of the bindings.  No public API."""
 from __future__ import annotations
 
 import torch
