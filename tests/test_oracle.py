@@ -1,8 +1,9 @@
 """The CPU restatement (oracle/gsr_oracle.c) checked three ways (no GPU needed):
   1. fp64 forward == a dense differentiable torch formulation of the same algorithm (tests/torch_reference.py);
-  2. fp64 analytic backward == torch autograd of that formulation (the reference's gradient conventions are
-     avoided in the scene: opacity <= 0.95 so the 0.99 clamp never binds, all means inside the 1.3 tan-fov
-     guard; denom2inv's +1e-7 bounds the agreement to ~1e-5 relative);
+  2. fp64 analytic backward == torch autograd of that formulation, also where the reference's two gradient
+     conventions bind (the 0.99 alpha clamp and the 1.3 tan-fov guard, written in autograd terms by
+     torch_reference.render(conventions="reference")); denom2inv's +1e-7 bounds the agreement to ~1e-5
+     relative;
   3. regression against the committed fixture tests/golden/oracle_scene.npz (see make_golden.py).
 """
 import os
@@ -18,7 +19,7 @@ from gsr_testutil import gs, make_camera, oracle_cam
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
 
-def _torch_run(scene, cam, bg, grads, deg):
+def _torch_run(scene, cam, bg, grads, deg, conventions="autograd"):
     dt = torch.float64
     t = {k: torch.tensor(scene[k], dtype=dt, requires_grad=True)
          for k in ("means3D", "scales", "rotations", "opacities", "shs")}
@@ -26,7 +27,8 @@ def _torch_run(scene, cam, bg, grads, deg):
     view, proj, campos = tr.camera_tensors(cam)
     color, radii, depth, alpha = tr.render(t["means3D"], m2d, t["opacities"], view, proj, campos, cam["tanx"],
                                            cam["tany"], cam["W"], cam["H"], torch.tensor(bg, dtype=dt),
-                                           sh=t["shs"], deg=deg, scales=t["scales"], rotations=t["rotations"])
+                                           sh=t["shs"], deg=deg, scales=t["scales"], rotations=t["rotations"],
+                                           conventions=conventions)
     gc, gd, ga = (torch.tensor(g, dtype=dt) for g in grads)
     ((color * gc).sum() + (depth * gd).sum() + (alpha * ga).sum()).backward()
     out = dict(color=color.detach().numpy(), depth=depth.detach().numpy(), alpha=alpha.detach().numpy(),
@@ -48,6 +50,59 @@ def test_oracle_matches_torch_autograd(deg, W, H, bgv):
     for k in ("color", "depth", "alpha"):
         np.testing.assert_allclose(f[k], ref[k], rtol=1e-9, atol=1e-10, err_msg=k)
     b = oracle.backward(scene, oracle_cam(cam), bg, *grads, prec="f64")
+    pairs = dict(means3D="means3D", scales="scales", rotations="rotations", opacities="opacity", shs="sh",
+                 means2D="means2D")
+    for tk, ok in pairs.items():
+        g_ref, g_or = ref["g_" + tk], b[ok].reshape(ref["g_" + tk].shape)
+        scale = max(1e-6, np.abs(g_ref).max())
+        err = np.abs(g_or - g_ref).max() / scale
+        assert err < 5e-5, f"{tk}: max rel err {err:.2e} (scale {scale:.3g})"
+
+
+def conventions_case(camera, W, H, deg):
+    """150 - 200 Gaussians seen by a camera of tests/camera_cases.py: the guard binds on visible Gaussians in x and
+    in y, and a few opacities at the top of their range make the 0.99 clamp bind."""
+    import camera_cases as cc
+
+    scene = gs.make_scene(200 if camera == "near49" else 150, sh_degree=deg, seed=30 + deg,
+                          radius=1.0 if camera == "near49" else 0.6, opacity_range=(0.3, 1.0))
+    scene["opacities"][::4] = 1.0
+    return scene, cc.camera(camera, W, H)
+
+
+@pytest.mark.parametrize("camera,W,H,deg,bgv", [("near49", 48, 40, 1, 1.0), ("inside", 40, 40, 0, 0.3),
+                                               ("offaxis", 48, 32, 2, 0.0)])
+def test_oracle_matches_torch_autograd_where_the_conventions_bind(camera, W, H, deg, bgv):
+    """The reference's gradient conventions, checked independently of the oracle's own reading of them: where
+    the guard binds, the clamped view coordinate is a constant (no gradient to t.x, d/dt.z with t.x held fixed);
+    where alpha is clamped to 0.99, the forward is clamped and the gradient is that of o G."""
+    import camera_cases as cc
+
+    scene, cam = conventions_case(camera, W, H, deg)
+    bg = np.full(3, bgv, np.float32)
+    grads = gs.upstream_grads(H, W, seed=deg)
+    oc = oracle_cam(cam)
+    # the scene reaches the branches: visible Gaussians beyond the guard, (pixel, Gaussian) pairs at the clamp
+    f = oracle.forward(scene, oc, bg, "f64")
+    a = oracle.gauss_aux(scene, oc, "f64")
+    vis = f["radii"] > 0
+    t = cc.view_space(scene["means3D"], cam)
+    bx = vis & (np.abs(t[:, 0] / t[:, 2]) > 1.3 * float(np.float32(cam["tanx"])))
+    by = vis & (np.abs(t[:, 1] / t[:, 2]) > 1.3 * float(np.float32(cam["tany"])))
+    assert bx.sum() >= 5 and by.sum() >= 5, (int(bx.sum()), int(by.sum()))
+    ys, xs = np.mgrid[0:H, 0:W]
+    dx, dy = a["px"][vis, None, None] - xs, a["py"][vis, None, None] - ys
+    cn = a["conic"][vis]
+    power = -0.5 * (cn[:, 0, None, None] * dx * dx + cn[:, 2, None, None] * dy * dy) - cn[:, 1, None, None] * dx * dy
+    assert (a["opacity"][vis, None, None] * np.exp(power) > 0.99).sum() >= 20
+    # cov2D determinants (0.3 dilation: >= 0.09) keep denom2inv's +1e-7 below 1.3e-5 relative
+    assert (1.0 / (a["conic"][vis, 0] * a["conic"][vis, 2] - a["conic"][vis, 1] ** 2)).min() > 0.089
+
+    ref = _torch_run(scene, cam, bg, grads, deg, conventions="reference")
+    np.testing.assert_array_equal(f["radii"], ref["radii"])
+    for k in ("color", "depth", "alpha"):
+        np.testing.assert_allclose(f[k], ref[k], rtol=1e-9, atol=1e-10, err_msg=k)
+    b = oracle.backward(scene, oc, bg, *grads, prec="f64")
     pairs = dict(means3D="means3D", scales="scales", rotations="rotations", opacities="opacity", shs="sh",
                  means2D="means2D")
     for tk, ok in pairs.items():

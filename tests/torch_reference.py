@@ -6,9 +6,10 @@ kernels: 16x16 tile binning from the 3-sigma radius rect, per-tile (depth, index
 min(0.99, o e^power), skip alpha < 1/255, stop at T (1 - alpha) < 1e-4, +0.3 EWA dilation, SH + 0.5
 clamped at 0.  The discrete decisions (culling, radius, skip/stop masks) are taken on detached values;
 gradients flow through everything else, so autograd equals the reference's analytic gradient except
-for its documented conventions (0.99 clamp ignored, frustum-clamp zeroing, denom2inv + 1e-7), which
-the tests avoid or bound.  means2D is added to the projected NDC xy, so its gradient is the
-reference's viewspace gradient (pixel gradient x W/2, H/2).
+for its documented conventions (0.99 clamp ignored, frustum-clamp zeroing, denom2inv + 1e-7): the first
+two are written in autograd terms by render(conventions="reference"), the third the tests bound.
+means2D is added to the projected NDC xy, so its gradient is the reference's viewspace gradient
+(pixel gradient x W/2, H/2).
 """
 from __future__ import annotations
 
@@ -50,8 +51,12 @@ def rot_matrix(q):
 
 
 def render(means3D, means2D, opacities, view, proj, campos, tanx, tany, W, H, bg, sh=None, deg=0, colors=None,
-           scales=None, rotations=None, cov3D=None, mod=1.0):
-    """Returns (color (3,H,W), radii (P,), depth (1,H,W), alpha (1,H,W))."""
+           scales=None, rotations=None, cov3D=None, mod=1.0, conventions="autograd"):
+    """Returns (color (3,H,W), radii (P,), depth (1,H,W), alpha (1,H,W)).
+
+    conventions="autograd" differentiates torch.clamp and clamp_max as they are; "reference" writes the
+    reference's two gradient conventions in autograd terms (same forward): a frustum-guard coordinate that
+    binds is a constant (tx = (lim tz).detach()), and alpha = a + (min(a, 0.99) - a).detach()."""
     dt = means3D.dtype
     P = means3D.shape[0]
     M4v = view.reshape(4, 4).to(dt)
@@ -81,6 +86,14 @@ def render(means3D, means2D, opacities, view, proj, campos, tanx, tany, W, H, bg
     tx = torch.clamp(t[:, 0] / t[:, 2], -limx, limx) * t[:, 2]
     ty = torch.clamp(t[:, 1] / t[:, 2], -limy, limy) * t[:, 2]
     tz = t[:, 2]
+    if conventions == "reference":
+        # where the guard binds the reference treats the clamped coordinate as a constant: no gradient to
+        # t.x (t.y), and d/dt.z of the Jacobian taken with that coordinate held fixed
+        with torch.no_grad():
+            bx = (t[:, 0] / t[:, 2]).abs() > limx
+            by = (t[:, 1] / t[:, 2]).abs() > limy
+        tx = torch.where(bx, tx.detach(), tx)
+        ty = torch.where(by, ty.detach(), ty)
     zero = torch.zeros_like(tz)
     J = torch.stack([torch.stack([fx / tz, zero, -fx * tx / tz ** 2], -1),
                      torch.stack([zero, fy / tz, -fy * ty / tz ** 2], -1)], -2)
@@ -140,7 +153,11 @@ def render(means3D, means2D, opacities, view, proj, campos, tanx, tany, W, H, bg
                 dx = px[idx][None, :] - pxy[:, 0:1]
                 dy = py[idx][None, :] - pxy[:, 1:2]
                 power = -0.5 * (ca[idx][None] * dx * dx + cc[idx][None] * dy * dy) - cb[idx][None] * dx * dy
-                alpha = torch.clamp_max(op[idx][None] * torch.exp(power), 0.99)
+                alpha = op[idx][None] * torch.exp(power)
+                if conventions == "reference":  # clamped forward, the gradient of the unclamped product
+                    alpha = alpha + (torch.clamp_max(alpha, 0.99) - alpha).detach()
+                else:
+                    alpha = torch.clamp_max(alpha, 0.99)
                 with torch.no_grad():
                     m0 = (power <= 0) & (alpha >= 1.0 / 255.0)
                     am = torch.where(m0, alpha, torch.zeros_like(alpha))
