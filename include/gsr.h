@@ -81,8 +81,11 @@ const char* gsr_version(void);
  *      as-rigid-as-possible energy of the deformed vertices, for all frames of a batch);
  *      gsr_sugar_spline_workspace_bytes / gsr_sugar_spline_forward / gsr_sugar_spline_backward (dynamic SuGaR: the
  *      B-spline from the control knots to the timed node attributes).
+ *   9  the gsr_sugar_*_forward / _backward calls take their stage's inputs as one struct (gsr_sugar_field, _normal,
+ *      _mesh, _skin, _timed, _arap, _spline) followed by the tables, gradients, outputs and workspace, which stay
+ *      positional; the *_workspace_bytes sizers are unchanged.
  */
-#define GSR_ABI_VERSION 8
+#define GSR_ABI_VERSION 9
 int gsr_abi_version(void);
 /* Message of the last failing call on this thread ("" if none). */
 const char* gsr_last_error(void);
@@ -444,10 +447,7 @@ int gsr_knn_points(int P, int K, const float* points, float* dists, long long* i
  * The neighbour density field of the SuGaR regulariser: replaces the gathers, the batched matmul and the sum of
  * SuGaRRegularizer.get_field_values (utils/sugar_utils.py:296-310), the `average` beta of get_beta (:423), and the
  * index_put scatter of their autograd backward.  M samples, K neighbour slots (1 <= K <= GSR_KNN_MAX_K), N Gaussians,
- * M K < 2^31.  All float arrays fp32:
- *   x (M,3) sample points;  nbr (R,K) int64 neighbour table;  row (M,) int64 or NULL;
- *   centers (N,3);  inv_sr (N,3,3) row-major = R[i][j] / max(s[j], 1e-8), what get_covariance(return_full_matrix=True,
- *   return_sqrt=True, inverse_scales=True) returns;  strengths (N,);  min_scale (N,) = scaling.min(-1).
+ * M K < 2^31.  The inputs are the fields of gsr_sugar_field below; all float arrays fp32.
  * With row, sample m reads the table row nbr[row[m]] (the reference's knn_idx[gaussian_idx], R = N, never gathered
  * into an (M,K) copy); with row NULL, R must equal M and sample m reads nbr[m] (closest_gaussians_idx).
  * For slot k with j = nbr[..][k]:
@@ -478,14 +478,23 @@ int gsr_knn_points(int P, int K, const float* points, float* dists, long long* i
  * records) only.  Kernels run on `stream`; the library allocates nothing.  M = 0 launches nothing and writes
  * nothing (the caller zeroes the N-sized gradients of an empty batch).
  */
+typedef struct gsr_sugar_field {
+  int M, K, N, R;       /* samples, neighbour slots, Gaussians, rows of nbr */
+  const float* x;       /* (M,3) sample points */
+  const long long* nbr; /* (R,K) int64 neighbour table */
+  const long long* row; /* (M,) int64, the table row of each sample, or NULL (then R = M) */
+  const float* centers; /* (N,3) */
+  /* (N,3,3) row-major = R[i][j] / max(s[j], 1e-8), what get_covariance(return_full_matrix=True, return_sqrt=True,
+   * inverse_scales=True) returns */
+  const float* inv_sr;
+  const float* strengths; /* (N,) */
+  const float* min_scale; /* (N,) = scaling.min(-1) */
+  float density_factor;
+} gsr_sugar_field;
 size_t gsr_sugar_field_workspace_bytes(int M, int K, int N);
-int gsr_sugar_field_forward(int M, int K, int N, int R, const float* x, const long long* nbr, const long long* row,
-                            const float* centers, const float* inv_sr, const float* strengths, const float* min_scale,
-                            float density_factor, float* density, float* beta_avg, float* op, void* workspace,
+int gsr_sugar_field_forward(const gsr_sugar_field* in, float* density, float* beta_avg, float* op, void* workspace,
                             size_t workspace_bytes, void* stream);
-int gsr_sugar_field_backward(int M, int K, int N, int R, const float* x, const long long* nbr, const long long* row,
-                             const float* centers, const float* inv_sr, const float* strengths, const float* min_scale,
-                             float density_factor, const float* dL_ddensity, const float* dL_dbeta_avg,
+int gsr_sugar_field_backward(const gsr_sugar_field* in, const float* dL_ddensity, const float* dL_dbeta_avg,
                              const float* dL_dop, float* dL_dx, float* dL_dcenters, float* dL_dinv_sr,
                              float* dL_dstrengths, float* dL_dmin_scale, void* workspace, size_t workspace_bytes,
                              void* stream);
@@ -494,13 +503,11 @@ int gsr_sugar_field_backward(int M, int K, int N, int R, const float* x, const l
  * The neighbour-normal loss of the SuGaR regulariser ("sdf better normal loss"): replaces the (M,K,3) gathers, the
  * sign flip, the weight normalisation and the weighted normal sum of coarse_density_regulation
  * (utils/sugar_utils.py:725-757) and the index_put scatter of their autograd backward.  M samples, K neighbour slots
- * (1 <= K <= GSR_KNN_MAX_K), N Gaussians, M (K + 1) < 2^31.  All float arrays fp32:
- *   x (M,3) sample points;  gaussian_idx (M,) int64, the Gaussian i each sample was drawn in;  nbr (R,K) int64;
- *   centers (N,3);  normals (N,3), need not be unit length;  min_scale (N,) = scaling.min(-1);
- *   op (M,K), the closest_gaussian_opacities of gsr_sugar_field_forward for the same samples and table.
- * With nbr_per_sample = 0, sample m reads the table row nbr[gaussian_idx[m]] (the reference's knn_idx, R = N, never
- * gathered into an (M,K) copy); with nbr_per_sample != 0, R must equal M and sample m reads nbr[m].
- * For slot k with j = nbr[..][k] and i = gaussian_idx[m]:
+ * (1 <= K <= GSR_KNN_MAX_K), N Gaussians, M (K + 1) < 2^31.  The inputs are the fields of gsr_sugar_normal below; all
+ * float arrays fp32.
+ * With per_sample = 0, sample m reads the table row nbr[own[m]] (the reference's knn_idx, R = N, never gathered into
+ * an (M,K) copy); with per_sample != 0, R must equal M and sample m reads nbr[m].
+ * For slot k with j = nbr[..][k] and i = own[m]:
  *   s_k = sign(n_j . n_i)  (sign(0) = 0);   a_k = |(x_m - c_j) . (s_k n_j)|
  *   w_k = op[m,k] a_k / max(min_scale_j, 1e-6)^2;   W = sum_k w_k;   Wc = max(W, 1e-6);   wh_k = w_k / Wc
  *   r = n_i - sum_k wh_k s_k n_j;   loss[m] = r . r
@@ -512,7 +519,7 @@ int gsr_sugar_field_backward(int M, int K, int N, int R, const float* x, const l
  *   r = (1 - W / Wc) n_i + sum_k wh_k (n_i - s_k n_j),      1 - W / Wc taken as exactly 0 when W >= 1e-6,
  * which spares the cancellation of n_i against the sample's own slot (j = i: that term is exactly 0).
  * Out of range: a slot whose j is outside [0, N) (the -1 padding of gsr_knn_points included) contributes nothing to
- * the loss or to any gradient, and j is never dereferenced.  A sample whose gaussian_idx[m] is outside [0, N), or
+ * the loss or to any gradient, and j is never dereferenced.  A sample whose own[m] is outside [0, N), or
  * outside [0, R) when it selects the table row, has loss[m] = 0 and no gradient; no row is read for it.
  * NaN inputs: unspecified values, no out-of-bounds access.
  * rec (M,4), 16-byte aligned (checked: GSR_EINVAL otherwise), may be NULL in a forward no backward follows: the forward writes (r, Wc) per sample
@@ -537,28 +544,34 @@ int gsr_sugar_field_backward(int M, int K, int N, int R, const float* x, const l
  * run on `stream`; the library allocates nothing.  M = 0 launches nothing and writes nothing (the caller zeroes the
  * gradient of an empty batch).
  */
+typedef struct gsr_sugar_normal {
+  int M, K, N, R;         /* samples, neighbour slots, Gaussians, rows of nbr */
+  const float* x;         /* (M,3) sample points */
+  const long long* own;   /* (M,) int64, the Gaussian i each sample was drawn in (gaussian_idx) */
+  const long long* nbr;   /* (R,K) int64 neighbour table */
+  int per_sample;         /* != 0: nbr has one row per sample; 0: sample m reads row own[m] */
+  const float* centers;   /* (N,3) */
+  const float* normals;   /* (N,3), need not be unit length */
+  const float* min_scale; /* (N,) = scaling.min(-1) */
+  const float* op;        /* (M,K), the op of gsr_sugar_field_forward for the same samples and table */
+} gsr_sugar_normal;
 size_t gsr_sugar_normal_workspace_bytes(int M, int K, int N);
-int gsr_sugar_normal_forward(int M, int K, int N, int R, const float* x, const long long* gaussian_idx,
-                             const long long* nbr, int nbr_per_sample, const float* centers, const float* normals,
-                             const float* min_scale, const float* op, float* loss, float* rec, void* workspace,
+int gsr_sugar_normal_forward(const gsr_sugar_normal* in, float* loss, float* rec, void* workspace,
                              size_t workspace_bytes, void* stream);
-int gsr_sugar_normal_backward(int M, int K, int N, int R, const float* x, const long long* gaussian_idx,
-                              const long long* nbr, int nbr_per_sample, const float* centers, const float* normals,
-                              const float* min_scale, const float* op, const float* rec, const float* dL_dloss,
-                              float* dL_dnormals, void* workspace, size_t workspace_bytes, void* stream);
+int gsr_sugar_normal_backward(const gsr_sugar_normal* in, const float* rec, const float* dL_dloss, float* dL_dnormals,
+                              void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * The geometry of SuGaR Gaussians bound to a mesh: replaces SuGaRModel.points, .scaling, .quaternions and
  * .get_gs_normals (geometry/sugar.py:449-536), i.e. the (F,3,3) vertex gather, the pytorch3d face normals, the three
  * normalisations, the two cross products, the (N,3,3) concatenation, matrix_to_quaternion and the index_put scatter of
  * their autograd backward.  V vertices, F faces, G Gaussians per face (1 <= G <= GSR_MESH_MAX_G), N = F G (passed,
- * and checked: GSR_EINVAL otherwise), N < 2^31:
- *   verts (V,3) fp32;  faces (F,3) int32;  bary (G,3) fp32 in HOST memory (read during the call);
- *   complex_numbers (N,2) fp32, the in-plane rotation;  log_scales (N,2) fp32;  thickness, the normal-axis scale.
+ * and checked: GSR_EINVAL otherwise), N < 2^31.  The inputs are the fields of gsr_sugar_mesh below and, positional,
+ *   bary (G,3) fp32 in HOST memory (read during the call);  thickness, the normal-axis scale (forward only).
  * Gaussian f G + g belongs to face f.  With p0, p1, p2 = verts[faces[f]] and normalize(v, eps) = v / max(|v|, eps):
  *   c = (p1 - p0) x (p2 - p0);   n = normalize(c, 1e-6) (pytorch3d's face normal);   R0 = normalize(n, 1e-12)
  *   b1 = normalize(p0 - p1, 1e-12);   b2 = normalize(R0 x b1, 1e-12)
- *   z = normalize(complex_numbers, 1e-12);   R1 = z0 b1 + z1 b2;   R2 = -z1 b1 + z0 b2
+ *   z = normalize(cplx, 1e-12);   R1 = z0 b1 + z1 b2;   R2 = -z1 b1 + z0 b2
  *   q = matrix_to_quaternion([R0 | R1 | R2]) (columns): with a_i = sqrt_pos of 1+m00+m11+m22, 1+m00-m11-m22,
  *   1-m00+m11-m22, 1-m00-m11+m22 (sqrt_pos(x) = sqrt(x) for x > 0, else 0 with zero gradient), the candidate rows
  *   (a0^2, m21-m12, m02-m20, m10-m01), (m21-m12, a1^2, m10+m01, m02+m20), (m02-m20, m10+m01, a2^2, m12+m21),
@@ -567,7 +580,7 @@ int gsr_sugar_normal_backward(int M, int K, int N, int R, const float* x, const 
  *   xyz = sum_k bary[g][k] p_k;   scaling = (thickness, exp(log_scales));   rotation = normalize(q, 1e-12);
  *   normals = R0 (the same for the G Gaussians of a face).
  * Outputs xyz (N,3), scaling (N,3), rotation (N,4), normals (N,3), all required.  rotation and dL_drotation must be
- * 16-byte aligned, complex_numbers, log_scales and their gradients 8-byte aligned (checked: GSR_EINVAL otherwise).
+ * 16-byte aligned, cplx, log_scales and their gradients 8-byte aligned (checked: GSR_EINVAL otherwise).
  * Precision: the per-face frame, the per-Gaussian part and the gradient arithmetic are all evaluated in fp64 from the
  * fp32 inputs; every output and gradient is rounded to fp32 once, except dL_dverts: its per-corner terms are rounded
  * to fp32 once (the corner rows), added in fp64 and the sum rounded once.
@@ -589,12 +602,17 @@ int gsr_sugar_normal_backward(int M, int K, int N, int R, const float* x, const 
  * forward is one launch, the backward two.  F = 0 launches nothing and writes nothing (the caller zeroes dL_dverts).
  */
 #define GSR_MESH_MAX_G 8
+typedef struct gsr_sugar_mesh {
+  int V, F, G;             /* vertices, faces, Gaussians per face */
+  const float* verts;      /* (V,3) */
+  const int* faces;        /* (F,3) int32 */
+  const float* cplx;       /* (F G,2) complex_numbers, the in-plane rotation; 8-byte aligned */
+  const float* log_scales; /* (F G,2); 8-byte aligned */
+} gsr_sugar_mesh;
 size_t gsr_sugar_mesh_workspace_bytes(int F, int V);
-int gsr_sugar_mesh_forward(int V, int F, int G, int N, const float* verts, const int* faces, const float* bary,
-                           const float* complex_numbers, const float* log_scales, float thickness, float* xyz,
+int gsr_sugar_mesh_forward(const gsr_sugar_mesh* in, int N, const float* bary, float thickness, float* xyz,
                            float* scaling, float* rotation, float* normals, void* stream);
-int gsr_sugar_mesh_backward(int V, int F, int G, int N, const float* verts, const int* faces, const float* bary,
-                            const float* complex_numbers, const float* log_scales, const int* corner_order,
+int gsr_sugar_mesh_backward(const gsr_sugar_mesh* in, int N, const float* bary, const int* corner_order,
                             const int* vert_offsets, const float* dL_dxyz, const float* dL_dscaling,
                             const float* dL_drotation, const float* dL_dnormals, float* dL_dverts, float* dL_dcomplex,
                             float* dL_dlog_scales, void* workspace, size_t workspace_bytes, void* stream);
@@ -612,9 +630,7 @@ int gsr_sugar_mesh_backward(int V, int F, int G, int N, const float* verts, cons
  *
  * gsr_sugar_skin_*: the deformation-graph skinning of the mesh vertices (_get_timed_vertex_attributes_from_dg,
  * dynamic_sugar.py:505-575).  T frames, V vertices, P nodes, K nodes per vertex (1 <= K <= GSR_SKIN_MAX_K);
- * T V, T P and V K < 2^31.
- *   verts (V,3);  node_xyz (P,3);  node_trans (T,P,3);  node_rots (T,P,4) xyzw, non-zero, any norm, 16-byte aligned;
- *   node_scales (T,P,3) or NULL;  nbr (V,K) int32, the nodes of a vertex;  w (V,K) fp32, their weights.
+ * T V, T P and V K < 2^31.  The inputs are the fields of gsr_sugar_skin below.
  * With q^ = q / |q| per (t, node) and p = verts[v], the sums over the K nodes of v in ascending k, from 0:
  *   GSR_SKIN_DQS:  d = 1/2 (trans, 0) (x) q^;   S_r = sum w_k q^_k;   S_d = sum w_k d_k;   m = |S_r|;
  *                  r = S_r / m;   e = S_d / m;   vert_xyz = R(r) p + 2 vec(e (x) conj(r))   (no antipodal sign fix)
@@ -645,9 +661,8 @@ int gsr_sugar_mesh_backward(int V, int F, int G, int N, const float* verts, cons
  *
  * gsr_sugar_timed_*: the Gaussians of the deformed mesh (get_timed_gs_attributes, fuse_rotations and
  * get_timed_gs_normals, dynamic_sugar.py:329-346, 618-688).  F faces, G Gaussians per face (1 <= G <=
- * GSR_MESH_MAX_G), N = F G (passed and checked); T N and T V < 2^31.
- *   vert_xyz (T,V,3);  vert_rot (T,V,4) xyzw, non-zero;  rotation0 (N,4) wxyz, the static rotation;  faces (F,3)
- *   int32;  bary (G,3) fp32 in HOST memory;  vert_scale (T,V,3) and log_scales (N,2): both or neither;  thickness.
+ * GSR_MESH_MAX_G), N = F G (passed and checked); T N and T V < 2^31.  The inputs are the fields of gsr_sugar_timed
+ * below and, positional, bary (G,3) fp32 in HOST memory.
  * For Gaussian n = f G + g, with i_c = faces[f][c] and b = bary[g]:
  *   xyz[t,n] = sum_c b_c vert_xyz[t,i_c];   phi = sum_c b_c Log(vert_rot[t,i_c]);
  *   rotation[t,n] = normalize(Exp(phi) (x) q0, 1e-12) stored wxyz, q0 = rotation0[n] read as xyzw;
@@ -669,25 +684,38 @@ int gsr_sugar_mesh_backward(int V, int F, int G, int N, const float* verts, cons
 #define GSR_SKIN_MAX_K 32
 #define GSR_SKIN_DQS 0
 #define GSR_SKIN_LBS 1
+typedef struct gsr_sugar_skin {
+  int T, V, P, K;           /* frames, vertices, nodes, nodes per vertex */
+  int method;               /* GSR_SKIN_DQS or GSR_SKIN_LBS */
+  const float* verts;       /* (V,3) */
+  const float* node_xyz;    /* (P,3) */
+  const float* node_trans;  /* (T,P,3) */
+  const float* node_rots;   /* (T,P,4) xyzw, non-zero, any norm; 16-byte aligned */
+  const float* node_scales; /* (T,P,3) or NULL */
+  const int* nbr;           /* (V,K) int32, the nodes of a vertex */
+  const float* w;           /* (V,K) fp32, their weights */
+} gsr_sugar_skin;
 size_t gsr_sugar_skin_workspace_bytes(int T, int V, int P);
-int gsr_sugar_skin_forward(int T, int V, int P, int K, int method, const float* verts, const float* node_xyz,
-                           const float* node_trans, const float* node_rots, const float* node_scales, const int* nbr,
-                           const float* w, float* vert_xyz, float* vert_rot, float* vert_scale, void* workspace,
-                           size_t workspace_bytes, void* stream);
-int gsr_sugar_skin_backward(int T, int V, int P, int K, int method, const float* verts, const float* node_xyz,
-                            const float* node_trans, const float* node_rots, const float* node_scales, const int* nbr,
-                            const float* w, const int* item_order, const int* node_offsets, const float* dL_dxyz,
-                            const float* dL_drot, const float* dL_dscale, float* dL_dverts, float* dL_dnode_trans,
-                            float* dL_dnode_rots, float* dL_dnode_scales, void* workspace, size_t workspace_bytes,
-                            void* stream);
+int gsr_sugar_skin_forward(const gsr_sugar_skin* in, float* vert_xyz, float* vert_rot, float* vert_scale,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int gsr_sugar_skin_backward(const gsr_sugar_skin* in, const int* item_order, const int* node_offsets,
+                            const float* dL_dxyz, const float* dL_drot, const float* dL_dscale, float* dL_dverts,
+                            float* dL_dnode_trans, float* dL_dnode_rots, float* dL_dnode_scales, void* workspace,
+                            size_t workspace_bytes, void* stream);
+typedef struct gsr_sugar_timed {
+  int T, V, F, G;          /* frames, vertices, faces, Gaussians per face */
+  const float* vert_xyz;   /* (T,V,3) */
+  const float* vert_rot;   /* (T,V,4) xyzw, non-zero; 16-byte aligned */
+  const float* rotation0;  /* (F G,4) wxyz, the static rotation; 16-byte aligned */
+  const float* vert_scale; /* (T,V,3), with log_scales: both or neither */
+  const float* log_scales; /* (F G,2); 8-byte aligned */
+  const int* faces;        /* (F,3) int32 */
+  float thickness;         /* the normal-axis scale */
+} gsr_sugar_timed;
 size_t gsr_sugar_timed_workspace_bytes(int T, int F);
-int gsr_sugar_timed_forward(int T, int V, int F, int G, int N, const float* vert_xyz, const float* vert_rot,
-                            const float* rotation0, const int* faces, const float* bary, const float* vert_scale,
-                            const float* log_scales, float thickness, float* xyz, float* rotation, float* normals,
-                            float* scaling, void* stream);
-int gsr_sugar_timed_backward(int T, int V, int F, int G, int N, const float* vert_xyz, const float* vert_rot,
-                             const float* rotation0, const int* faces, const float* bary, const float* vert_scale,
-                             const float* log_scales, float thickness, const int* corner_order,
+int gsr_sugar_timed_forward(const gsr_sugar_timed* in, int N, const float* bary, float* xyz, float* rotation,
+                            float* normals, float* scaling, void* stream);
+int gsr_sugar_timed_backward(const gsr_sugar_timed* in, int N, const float* bary, const int* corner_order,
                              const int* vert_offsets, const float* dL_dxyz, const float* dL_drotation,
                              const float* dL_dnormals, const float* dL_dscaling, float* dL_dvert_xyz,
                              float* dL_dvert_rot, float* dL_drotation0, float* dL_dvert_scale, float* dL_dlog_scales,
@@ -697,12 +725,8 @@ int gsr_sugar_timed_backward(int T, int V, int F, int G, int N, const float* ver
  * gsr_sugar_arap_*: the as-rigid-as-possible energy of the deformed vertices with given per-vertex rotations
  * (ARAPCoach.compute_arap_energy with vert_rotations, utils/arap_utils.py:148-189, which _compute_arap_energy of
  * system/sugar_4dgen.py calls once per frame), for all T frames of a batch.  V vertices, E directed one-ring edges;
- * T V < 2^31.
- *   verts (V,3): the rest vertices;  offsets (V+1,) int32, nbr (E,) int32, w (E,) fp32: the one-rings in CSR, vertex i
- *   owning entries offsets[i] .. offsets[i+1]), nbr the neighbour j, w the edge weight w_ij (the caller's: the
- *   reference's are cotangent weights and may be negative);  vert_xyz (T,V,3): the deformed vertices x';  vert_rot:
- *   rot_form GSR_ARAP_MATRIX: (T,V,3,3) row-major matrices R;  GSR_ARAP_QUAT: (T,V,4) xyzw quaternions of any norm,
- *   16-byte aligned, R = I + 2 w [v]x + 2 [v]x^2 (pypose's matrix(): no normalisation).
+ * T V < 2^31.  The inputs are the fields of gsr_sugar_arap below: the one-rings in CSR, vertex i owning the entries
+ * offsets[i] .. offsets[i+1]) of nbr and w.
  * With p_ij = verts[i] - verts[j] (formed here, exactly), d_ij = x'_i - x'_j and s_ij = d_ij - R_i p_ij at frame t:
  *   energy[t] = sum_i sum_{j in row i} w_ij |s_ij|^2                                             energy (T,)
  * Backward, given dL_denergy (T,) = g: writes in full
@@ -727,26 +751,34 @@ int gsr_sugar_timed_backward(int T, int V, int F, int G, int N, const float* ver
  */
 #define GSR_ARAP_QUAT 0
 #define GSR_ARAP_MATRIX 1
+typedef struct gsr_sugar_arap {
+  int T, V, E;           /* frames, vertices, directed one-ring edges */
+  int rot_form;          /* GSR_ARAP_QUAT or GSR_ARAP_MATRIX */
+  const float* verts;    /* (V,3): the rest vertices */
+  /* (E,) fp32: the edge weight w_ij (the caller's: the reference's are cotangent weights and may be negative) */
+  const float* w;
+  const float* vert_xyz; /* (T,V,3): the deformed vertices x' */
+  /* GSR_ARAP_MATRIX: (T,V,3,3) row-major matrices R;  GSR_ARAP_QUAT: (T,V,4) xyzw quaternions of any norm, 16-byte
+   * aligned, R = I + 2 w [v]x + 2 [v]x^2 (pypose's matrix(): no normalisation) */
+  const float* vert_rot;
+  const int* offsets;    /* (V+1,) int32 */
+  const int* nbr;        /* (E,) int32: the neighbour j */
+} gsr_sugar_arap;
 size_t gsr_sugar_arap_workspace_bytes(int T, int V);
-int gsr_sugar_arap_forward(int T, int V, int E, int rot_form, const float* verts, const int* offsets, const int* nbr,
-                           const float* w, const float* vert_xyz, const float* vert_rot, float* energy,
-                           void* workspace, size_t workspace_bytes, void* stream);
-int gsr_sugar_arap_backward(int T, int V, int E, int rot_form, const float* verts, const int* offsets, const int* nbr,
-                            const float* w, const float* vert_xyz, const float* vert_rot, const float* dL_denergy,
-                            float* dL_dvert_xyz, float* dL_dvert_rot, void* stream);
+int gsr_sugar_arap_forward(const gsr_sugar_arap* in, float* energy, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int gsr_sugar_arap_backward(const gsr_sugar_arap* in, const float* dL_denergy, float* dL_dvert_xyz,
+                            float* dL_dvert_rot, void* stream);
 
 /*
  * gsr_sugar_spline_*: the B-spline that turns the control knots of the deformation network into the timed node (or
  * vertex) attributes (Spline.forward, geometry/spline_utils.py:195-332, as get_timed_dg_attributes and
  * get_timed_vertex_attributes call it, dynamic_sugar.py:425-435, 488-494), for all T timestamps of a call.  P points,
- * n_knots knots, degree 1 or 3 (n_knots >= degree + 1); T P and n_knots P < 2^31.
- *   timestamps (T,);  knots_xyz (n_knots,P,3);  knots_rot (n_knots,P,4) xyzw, non-zero, any norm, 16-byte aligned;
- *   knots_scale (n_knots,P,3) or NULL: frame-major, as _get_timed_dg_attributes_wo_spline returns them (the
- *   reference's set_data tensors are their permute(1, 0, 2)).
- *   start_time, interval (> 0): the grid, knot k at start_time + k interval;  t_lo, t_hi: the clamp bounds (the
- *   reference's t_lower_bound + 1e-6 and t_upper_bound - 1e-6 as it forms them in fp32).
+ * n_knots knots, degree 1 or 3 (n_knots >= degree + 1); T P and n_knots P < 2^31.  The inputs are the fields of
+ * gsr_sugar_spline below; the knots are frame-major, as _get_timed_dg_attributes_wo_spline returns them (the
+ * reference's set_data tensors are their permute(1, 0, 2)).
  * The segment of a timestamp, in fp32 as the reference takes it (a discrete decision):
- *   ts = min(max(t, t_lo), t_hi);  nt = (ts - start_time) / interval (correctly rounded);  i = (int) floor(nt);
+ *   ts = min(max(t, lo), hi);  nt = (ts - start) / interval (correctly rounded);  i = (int) floor(nt);
  *   u = nt - (float) i;  degree 3: i -= 1;  then i is clamped to [0, n_knots - degree - 1], so that no timestamp (NaN
  *   included: its outputs are unspecified) reads outside the knots.
  * With k_j = knots[i + j][p], u taken to fp64, the sums in ascending j:
@@ -771,13 +803,19 @@ int gsr_sugar_arap_backward(int T, int V, int E, int rot_form, const float* vert
  * launch, the backward two, on `stream`; the library allocates nothing.  T = 0 or P = 0 launches nothing and writes
  * nothing (the caller zeroes the gradients).
  */
+typedef struct gsr_sugar_spline {
+  int T, P, n_knots, degree; /* timestamps, points, knots, 1 or 3 */
+  float start, interval;     /* the grid: knot k at start + k interval (interval > 0) */
+  /* the clamp bounds (the reference's t_lower_bound + 1e-6 and t_upper_bound - 1e-6 as it forms them in fp32) */
+  float lo, hi;
+  const float* timestamps;  /* (T,) */
+  const float* knots_xyz;   /* (n_knots,P,3) */
+  const float* knots_rot;   /* (n_knots,P,4) xyzw, non-zero, any norm; 16-byte aligned */
+  const float* knots_scale; /* (n_knots,P,3) or NULL */
+} gsr_sugar_spline;
 size_t gsr_sugar_spline_workspace_bytes(int T, int P, int degree);
-int gsr_sugar_spline_forward(int T, int P, int n_knots, int degree, float start_time, float interval, float t_lo,
-                             float t_hi, const float* timestamps, const float* knots_xyz, const float* knots_rot,
-                             const float* knots_scale, float* xyz, float* rot, float* scale, void* stream);
-int gsr_sugar_spline_backward(int T, int P, int n_knots, int degree, float start_time, float interval, float t_lo,
-                              float t_hi, const float* timestamps, const float* knots_xyz, const float* knots_rot,
-                              const float* knots_scale, const float* dL_dxyz, const float* dL_drot,
+int gsr_sugar_spline_forward(const gsr_sugar_spline* in, float* xyz, float* rot, float* scale, void* stream);
+int gsr_sugar_spline_backward(const gsr_sugar_spline* in, const float* dL_dxyz, const float* dL_drot,
                               const float* dL_dscale, float* dL_dknots_xyz, float* dL_dknots_rot,
                               float* dL_dknots_scale, void* workspace, size_t workspace_bytes, void* stream);
 

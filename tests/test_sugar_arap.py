@@ -2,6 +2,8 @@
 (V, V) restatement of tests/sugar_arap_reference.py (bitwise: both sides run the same torch float32 ops on this
 machine), the argument checks, and the properties that pin the energy restatement (the checker of the GPU tests in
 tests/test_gpu_sugar_arap.py)."""
+import ctypes
+
 import pytest
 
 from diff_gaussian_rasterization import _C
@@ -16,9 +18,9 @@ from sugar_cases import MESHES, mesh, random_quats  # noqa: E402
 NAMES = ("gsr_sugar_arap_workspace_bytes", "gsr_sugar_arap_forward", "gsr_sugar_arap_backward")
 D = torch.float64
 
-def test_library_has_the_entry_points_at_abi_8():
+def test_library_has_the_entry_points_at_abi_9():
     lib = _C.load_library()
-    assert _C.ABI_VERSION == 8 and lib.gsr_abi_version() == 8  # additive: the revision stays
+    assert _C.ABI_VERSION == 9 and lib.gsr_abi_version() == 9
     for name in NAMES:
         assert hasattr(lib, name) and name in _C.SIGNATURES
     assert set(sugar_arap.__all__) >= {"ArapBinding", "arap_energy"}
@@ -124,14 +126,21 @@ def test_energy_argument_checks():
 def test_c_entries_check_before_any_device_work():
     lib = _C.load_library()
     null = None
-    assert lib.gsr_sugar_arap_forward(0, 0, 0, 0, *[null] * 7, null, 0, null) == 0  # nothing to do
-    assert lib.gsr_sugar_arap_backward(0, 4, 0, 1, *[null] * 9, null) == 0
+
+    def arap(T, V, E, rot_form):  # (every pointer of the struct null)
+        return _C.SugarArap(T=T, V=V, E=E, rot_form=rot_form)
+
+    assert lib.gsr_sugar_arap_forward(arap(0, 0, 0, 0), null, null, 0, null) == 0  # nothing to do
+    assert lib.gsr_sugar_arap_backward(arap(0, 4, 0, 1), null, null, null, null) == 0
     for args, msg in (((1, 4, 6, 2), "rot_form"), ((-1, 4, 6, 0), "negative"), ((2 ** 16, 2 ** 15, 6, 0), "2^31"),
                       ((1, 4, 6, 0), "null pointer")):
-        assert lib.gsr_sugar_arap_forward(*args, *[null] * 7, null, 0, null) == 1
+        assert lib.gsr_sugar_arap_forward(arap(*args), null, null, 0, null) == 1
         assert msg in lib.gsr_last_error().decode()
-        assert lib.gsr_sugar_arap_backward(*args, *[null] * 9, null) == 1
+        assert lib.gsr_sugar_arap_backward(arap(*args), null, null, null, null) == 1
         assert msg in lib.gsr_last_error().decode()
+    v = ctypes.c_void_p(16)  # never dereferenced: a null struct fails first
+    assert lib.gsr_sugar_arap_forward(null, v, v, 1 << 40, null) == 1 and b"null pointer" in lib.gsr_last_error()
+    assert lib.gsr_sugar_arap_backward(null, v, v, v, null) == 1 and b"null pointer" in lib.gsr_last_error()
 
 
 # ---- the restatement ----------------------------------------------------------------------------------------------

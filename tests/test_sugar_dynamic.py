@@ -23,9 +23,9 @@ NAMES = ("gsr_sugar_skin_workspace_bytes", "gsr_sugar_skin_forward", "gsr_sugar_
 D = torch.float64
 
 
-def test_library_has_the_entry_points_at_abi_8():
+def test_library_has_the_entry_points_at_abi_9():
     lib = _C.load_library()
-    assert _C.ABI_VERSION == 8 and lib.gsr_abi_version() == 8  # additive: the revision stays
+    assert _C.ABI_VERSION == 9 and lib.gsr_abi_version() == 9
     for name in NAMES:
         assert hasattr(lib, name) and name in _C.SIGNATURES
 
@@ -297,16 +297,23 @@ def test_c_entries_check_their_arguments_without_gpu():
     v = ctypes.c_void_p(16)  # never dereferenced: the calls fail validation first
     big = 1 << 40
 
+    def skin(T, V, P, K, method, verts, nx, nt, nr, ns, nbr, w):
+        return _C.SugarSkin(T=T, V=V, P=P, K=K, method=method, verts=verts, node_xyz=nx, node_trans=nt, node_rots=nr,
+                            node_scales=ns, nbr=nbr, w=w)
+
     def sfwd(T=2, V=3, P=4, K=2, method=0, verts=v, nx=v, nt=v, nr=v, ns=None, nbr=v, w=v, xyz=v, rot=v, sc=None, ws=v,
              nbytes=big):
-        return lib.gsr_sugar_skin_forward(T, V, P, K, method, verts, nx, nt, nr, ns, nbr, w, xyz, rot, sc, ws, nbytes,
-                                          None)
+        return lib.gsr_sugar_skin_forward(skin(T, V, P, K, method, verts, nx, nt, nr, ns, nbr, w), xyz, rot, sc, ws,
+                                          nbytes, None)
 
     def sbwd(T=2, V=3, P=4, K=2, method=0, verts=v, nx=v, nt=v, nr=v, ns=None, nbr=v, w=v, io=v, no=v, g=(v, v, None),
              dv=v, dt=v, dr=v, ds=None, ws=v, nbytes=big):
-        return lib.gsr_sugar_skin_backward(T, V, P, K, method, verts, nx, nt, nr, ns, nbr, w, io, no, *g, dv, dt, dr, ds,
-                                           ws, nbytes, None)
+        return lib.gsr_sugar_skin_backward(skin(T, V, P, K, method, verts, nx, nt, nr, ns, nbr, w), io, no, *g, dv, dt,
+                                           dr, ds, ws, nbytes, None)
 
+    assert lib.gsr_sugar_skin_forward(None, v, v, None, v, big, None) == 1 and b"null" in lib.gsr_last_error()
+    assert lib.gsr_sugar_skin_backward(None, v, v, v, v, None, v, v, v, None, v, big, None) == 1
+    assert b"null" in lib.gsr_last_error()
     for call in (sfwd, sbwd):
         for K in (0, 33):
             assert call(K=K) == 1 and b"K must" in lib.gsr_last_error()
@@ -334,15 +341,23 @@ def test_c_entries_check_their_arguments_without_gpu():
 
     bary = (ctypes.c_float * 24)(*([1 / 3] * 24))
 
+    def timed(T, V, F, G, vx, vr, q0, faces, vs, ls):
+        return _C.SugarTimed(T=T, V=V, F=F, G=G, vert_xyz=vx, vert_rot=vr, rotation0=q0, vert_scale=vs, log_scales=ls,
+                             faces=faces, thickness=1e-3)
+
     def tfwd(T=2, V=4, F=2, G=3, N=6, vx=v, vr=v, q0=v, faces=v, bary=bary, vs=None, ls=None, xyz=v, rot=v, nrm=v,
              sc=None):
-        return lib.gsr_sugar_timed_forward(T, V, F, G, N, vx, vr, q0, faces, bary, vs, ls, 1e-3, xyz, rot, nrm, sc, None)
+        return lib.gsr_sugar_timed_forward(timed(T, V, F, G, vx, vr, q0, faces, vs, ls), N, bary, xyz, rot, nrm, sc,
+                                           None)
 
     def tbwd(T=2, V=4, F=2, G=3, N=6, vx=v, vr=v, q0=v, faces=v, bary=bary, vs=None, ls=None, co=v, vo=v,
              g=(v, v, v, None), dx=v, dr=v, dq0=v, dvs=None, dls=None, ws=v, nbytes=big):
-        return lib.gsr_sugar_timed_backward(T, V, F, G, N, vx, vr, q0, faces, bary, vs, ls, 1e-3, co, vo, *g, dx, dr,
+        return lib.gsr_sugar_timed_backward(timed(T, V, F, G, vx, vr, q0, faces, vs, ls), N, bary, co, vo, *g, dx, dr,
                                             dq0, dvs, dls, ws, nbytes, None)
 
+    assert lib.gsr_sugar_timed_forward(None, 6, bary, v, v, v, None, None) == 1 and b"null" in lib.gsr_last_error()
+    assert lib.gsr_sugar_timed_backward(None, 6, bary, v, v, v, v, v, None, v, v, v, None, None, v, big, None) == 1
+    assert b"null" in lib.gsr_last_error()
     for call in (tfwd, tbwd):
         assert call(N=7, vx=None, vr=None, q0=None, faces=None) == 1 and b"F x G" in lib.gsr_last_error()
         for G in (0, 9):

@@ -8,9 +8,9 @@ import pytest
 from diff_gaussian_rasterization import _C
 
 
-def test_library_has_the_entry_points_at_abi_8():
+def test_library_has_the_entry_points_at_abi_9():
     lib = _C.load_library()
-    assert _C.ABI_VERSION == 8 and lib.gsr_abi_version() == 8
+    assert _C.ABI_VERSION == 9 and lib.gsr_abi_version() == 9
     for name in ("gsr_sugar_field_workspace_bytes", "gsr_sugar_field_forward", "gsr_sugar_field_backward"):
         assert hasattr(lib, name) and name in _C.SIGNATURES
 
@@ -32,14 +32,20 @@ def test_argument_errors_without_gpu():
     v = ctypes.c_void_p(16)  # never dereferenced: the calls fail validation first
     big = 1 << 40
 
+    def field(M, K, N, R, x, nbr, row, centers):
+        return _C.SugarField(M=M, K=K, N=N, R=R, x=x, nbr=nbr, row=row, centers=centers, inv_sr=v, strengths=v,
+                             min_scale=v, density_factor=1.0)
+
     def fwd(M=10, K=4, N=5, R=10, x=v, nbr=v, row=None, centers=v, density=v, ws=v, nbytes=big):
-        return lib.gsr_sugar_field_forward(M, K, N, R, x, nbr, row, centers, v, v, v, 1.0, density, v, None, ws,
-                                           nbytes, None)
+        return lib.gsr_sugar_field_forward(field(M, K, N, R, x, nbr, row, centers), density, v, None, ws, nbytes, None)
 
     def bwd(M=10, K=4, N=5, R=10, row=None, dx=v, dcenters=v, nbytes=big):
-        return lib.gsr_sugar_field_backward(M, K, N, R, v, v, row, v, v, v, v, 1.0, v, None, None, dx, dcenters, v, v,
-                                            v, v, nbytes, None)
+        return lib.gsr_sugar_field_backward(field(M, K, N, R, v, v, row, v), v, None, None, dx, dcenters, v, v, v, v,
+                                            nbytes, None)
 
+    assert lib.gsr_sugar_field_forward(None, v, v, None, v, big, None) == 1 and b"null" in lib.gsr_last_error()
+    assert lib.gsr_sugar_field_backward(None, v, None, None, v, v, v, v, v, v, big, None) == 1
+    assert b"null" in lib.gsr_last_error()
     for call in (fwd, bwd):
         for K in (0, 33):
             assert call(K=K) == 1 and b"K" in lib.gsr_last_error()

@@ -20,9 +20,9 @@ from sugar_mesh import MeshBinding, bound_gaussians, initial_log_scales  # noqa:
 NAMES = ("gsr_sugar_mesh_workspace_bytes", "gsr_sugar_mesh_forward", "gsr_sugar_mesh_backward")
 
 
-def test_library_has_the_entry_points_at_abi_8():
+def test_library_has_the_entry_points_at_abi_9():
     lib = _C.load_library()
-    assert _C.ABI_VERSION == 8 and lib.gsr_abi_version() == 8  # additive: the revision stays
+    assert _C.ABI_VERSION == 9 and lib.gsr_abi_version() == 9
     for name in NAMES:
         assert hasattr(lib, name) and name in _C.SIGNATURES
 
@@ -168,18 +168,24 @@ def test_c_entries_check_their_arguments_without_gpu():
     bary = (ctypes.c_float * 24)(*([1 / 3] * 24))
     big = 1 << 40
 
+    def mesh(V, F, G, verts, faces, cplx, ls):
+        return _C.SugarMesh(V=V, F=F, G=G, verts=verts, faces=faces, cplx=cplx, log_scales=ls)
+
     def fwd(V=4, F=2, G=3, N=6, verts=v, faces=v, bary=bary, cplx=v, ls=v, xyz=v, sc=v, rot=v, nrm=v):
-        return lib.gsr_sugar_mesh_forward(V, F, G, N, verts, faces, bary, cplx, ls, 1e-3, xyz, sc, rot, nrm, None)
+        return lib.gsr_sugar_mesh_forward(mesh(V, F, G, verts, faces, cplx, ls), N, bary, 1e-3, xyz, sc, rot, nrm, None)
 
     def bwd(V=4, F=2, G=3, N=6, verts=v, faces=v, bary=bary, cplx=v, ls=v, co=v, vo=v, g=(v, v, v, v), dv=v, dc=v,
             dl=v, ws=v, nbytes=big):
-        return lib.gsr_sugar_mesh_backward(V, F, G, N, verts, faces, bary, cplx, ls, co, vo, *g, dv, dc, dl, ws, nbytes,
-                                           None)
+        return lib.gsr_sugar_mesh_backward(mesh(V, F, G, verts, faces, cplx, ls), N, bary, co, vo, *g, dv, dc, dl, ws,
+                                           nbytes, None)
 
+    assert lib.gsr_sugar_mesh_forward(None, 6, bary, 1e-3, v, v, v, v, None) == 1 and b"null" in lib.gsr_last_error()
+    assert lib.gsr_sugar_mesh_backward(None, 6, bary, v, v, v, v, v, v, v, v, v, v, big, None) == 1
+    assert b"null" in lib.gsr_last_error()
     # N != F x G: rejected with code 1 before the (null) device pointers are looked at
     for call in (fwd, bwd):
         assert call(N=7, verts=None, faces=None, cplx=None, ls=None) == 1 and b"F x G" in lib.gsr_last_error()
-    assert lib.gsr_sugar_mesh_forward(4, 2, 3, 5, None, None, bary, None, None, 1e-3, None, None, None, None, None) == 1
+    assert fwd(N=5, verts=None, faces=None, cplx=None, ls=None, xyz=None, sc=None, rot=None, nrm=None) == 1
     assert b"F x G" in lib.gsr_last_error()
     for call in (fwd, bwd):
         for G in (0, 9):

@@ -11,9 +11,9 @@ from diff_gaussian_rasterization import _C
 NAMES = ("gsr_sugar_normal_workspace_bytes", "gsr_sugar_normal_forward", "gsr_sugar_normal_backward")
 
 
-def test_library_has_the_entry_points_at_abi_8():
+def test_library_has_the_entry_points_at_abi_9():
     lib = _C.load_library()
-    assert _C.ABI_VERSION == 8 and lib.gsr_abi_version() == 8  # additive: the revision stays
+    assert _C.ABI_VERSION == 9 and lib.gsr_abi_version() == 9
     for name in NAMES:
         assert hasattr(lib, name) and name in _C.SIGNATURES
 
@@ -38,15 +38,19 @@ def test_argument_errors_without_gpu():
     big = 1 << 40
 
     def fwd(M=10, K=4, N=5, R=5, x=v, own=v, nbr=v, per_sample=0, centers=v, normals=v, op=v, loss=v, ws=v,
-            nbytes=big):
-        return lib.gsr_sugar_normal_forward(M, K, N, R, x, own, nbr, per_sample, centers, normals, v, op, loss, None,
-                                            ws, nbytes, None)
+            nbytes=big, rec=None):
+        s = _C.SugarNormal(M=M, K=K, N=N, R=R, x=x, own=own, nbr=nbr, per_sample=per_sample, centers=centers,
+                           normals=normals, min_scale=v, op=op)
+        return lib.gsr_sugar_normal_forward(s, loss, rec, ws, nbytes, None)
 
     def bwd(M=10, K=4, N=5, R=5, x=v, own=v, nbr=v, per_sample=0, centers=v, normals=v, op=v, rec=v, g=v, dn=v, ws=v,
             nbytes=big):
-        return lib.gsr_sugar_normal_backward(M, K, N, R, x, own, nbr, per_sample, centers, normals, v, op, rec, g, dn,
-                                             ws, nbytes, None)
+        s = _C.SugarNormal(M=M, K=K, N=N, R=R, x=x, own=own, nbr=nbr, per_sample=per_sample, centers=centers,
+                           normals=normals, min_scale=v, op=op)
+        return lib.gsr_sugar_normal_backward(s, rec, g, dn, ws, nbytes, None)
 
+    assert lib.gsr_sugar_normal_forward(None, v, None, v, big, None) == 1 and b"null" in lib.gsr_last_error()
+    assert lib.gsr_sugar_normal_backward(None, v, v, v, v, big, None) == 1 and b"null" in lib.gsr_last_error()
     for call in (fwd, bwd):
         for K in (0, 33):
             assert call(K=K) == 1 and b"K" in lib.gsr_last_error()
@@ -62,8 +66,7 @@ def test_argument_errors_without_gpu():
     assert fwd(loss=None) == 1
     odd = ctypes.c_void_p(24)  # rec is read and written as float4
     assert bwd(rec=odd) == 1 and b"aligned" in lib.gsr_last_error()
-    assert lib.gsr_sugar_normal_forward(10, 4, 5, 5, v, v, v, 0, v, v, v, v, v, odd, v, big, None) == 1
-    assert b"aligned" in lib.gsr_last_error()
+    assert fwd(rec=odd) == 1 and b"aligned" in lib.gsr_last_error()
     assert bwd(rec=None) == 1 and bwd(g=None) == 1 and bwd(dn=None) == 1
     assert fwd(nbytes=lib.gsr_sugar_normal_workspace_bytes(0, 4, 5) - 1) == 1
     assert bwd(nbytes=lib.gsr_sugar_normal_workspace_bytes(10, 4, 5) - 1) == 1

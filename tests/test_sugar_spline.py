@@ -40,9 +40,9 @@ def restated(dtype, z, degree, scale=True):
     return r
 
 
-def test_library_has_the_entry_points_at_abi_8():
+def test_library_has_the_entry_points_at_abi_9():
     lib = _C.load_library()
-    assert _C.ABI_VERSION == 8 and lib.gsr_abi_version() == 8  # additive: the revision stays
+    assert _C.ABI_VERSION == 9 and lib.gsr_abi_version() == 9
     for name in NAMES:
         assert hasattr(lib, name) and name in _C.SIGNATURES
 
@@ -254,16 +254,23 @@ def test_c_entries_check_their_arguments_without_gpu():
     odd = ctypes.c_void_p(24)
     big = 1 << 40
 
+    def spline(T, P, n, degree, start, interval, lo, hi, ts, kx, kr, ks):
+        return _C.SugarSpline(T=T, P=P, n_knots=n, degree=degree, start=start, interval=interval, lo=lo, hi=hi,
+                              timestamps=ts, knots_xyz=kx, knots_rot=kr, knots_scale=ks)
+
     def fwd(T=2, P=5, n=7, degree=3, start=-0.3, interval=0.3, lo=0.0, hi=1.2, ts=v, kx=v, kr=v, ks=None, xyz=v,
             rot=v, sc=None):
-        return lib.gsr_sugar_spline_forward(T, P, n, degree, start, interval, lo, hi, ts, kx, kr, ks, xyz, rot, sc,
-                                            None)
+        return lib.gsr_sugar_spline_forward(spline(T, P, n, degree, start, interval, lo, hi, ts, kx, kr, ks), xyz, rot,
+                                            sc, None)
 
     def bwd(T=2, P=5, n=7, degree=3, start=-0.3, interval=0.3, lo=0.0, hi=1.2, ts=v, kx=v, kr=v, ks=None,
             g=(v, v, None), dx=v, dr=v, ds=None, ws=v, nbytes=big):
-        return lib.gsr_sugar_spline_backward(T, P, n, degree, start, interval, lo, hi, ts, kx, kr, ks, *g, dx, dr, ds,
-                                             ws, nbytes, None)
+        return lib.gsr_sugar_spline_backward(spline(T, P, n, degree, start, interval, lo, hi, ts, kx, kr, ks), *g, dx,
+                                             dr, ds, ws, nbytes, None)
 
+    assert lib.gsr_sugar_spline_forward(None, v, v, None, None) == 1 and b"null" in lib.gsr_last_error()
+    assert lib.gsr_sugar_spline_backward(None, v, v, None, v, v, None, v, big, None) == 1
+    assert b"null" in lib.gsr_last_error()
     for call in (fwd, bwd):
         for degree in (0, 2, 4, -1):
             assert call(degree=degree) == 1 and b"degree must" in lib.gsr_last_error()

@@ -35,6 +35,14 @@ static int last_launch() {
   return GSR_OK;
 }
 
+// an empty problem: nothing to launch, no device touched
+static int nothing_to_do() {
+  g_err[0] = 0;
+  return GSR_OK;
+}
+
+static int null_argument() { return fail(GSR_EINVAL, "%s", "null pointer argument"); }
+
 // ---- phase profiler: event pairs on the launch stream, resolved lazily in gsr_profile_read ----
 namespace {
 struct PhaseEvents {
@@ -493,17 +501,15 @@ int gsr_knn_points(int P, int K, const float* points, float* dists, long long* i
 }
 
 // ---- the SuGaR neighbour density field (gsr_field.hip) ---------------------------------------------
-static int field_check(int M, int K, int N, int R, const float* x, const long long* nbr, const long long* row,
-                       const float* centers, const float* inv_sr, const float* strengths, const float* min_scale,
-                       FieldCall& c) {
-  if (K < 1 || K > GSR_KNN_MAX_K) return fail(GSR_EINVAL, "%s", "K must be in 1..32");
-  if (M < 0 || N < 0 || R < 0) return fail(GSR_EINVAL, "%s", "negative size");
-  if ((long long)M * K >= (1ll << 31)) return fail(GSR_EINVAL, "%s", "M x K must stay below 2^31: split the samples");
-  if (row == nullptr && R != M) return fail(GSR_EINVAL, "%s", "without row the neighbour table has M rows");
-  if (M > 0 && (x == nullptr || (R > 0 && nbr == nullptr))) return fail(GSR_EINVAL, "%s", "null pointer argument");
-  if (N > 0 && (centers == nullptr || inv_sr == nullptr || strengths == nullptr || min_scale == nullptr))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
-  c = FieldCall{M, K, N, R, x, nbr, row, centers, inv_sr, strengths, min_scale, 1.0f};
+static int field_check(const gsr_sugar_field& c) {
+  if (c.K < 1 || c.K > GSR_KNN_MAX_K) return fail(GSR_EINVAL, "%s", "K must be in 1..32");
+  if (c.M < 0 || c.N < 0 || c.R < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if ((long long)c.M * c.K >= (1ll << 31))
+    return fail(GSR_EINVAL, "%s", "M x K must stay below 2^31: split the samples");
+  if (c.row == nullptr && c.R != c.M) return fail(GSR_EINVAL, "%s", "without row the neighbour table has M rows");
+  if (c.M > 0 && (c.x == nullptr || (c.R > 0 && c.nbr == nullptr))) return null_argument();
+  if (c.N > 0 && (c.centers == nullptr || c.inv_sr == nullptr || c.strengths == nullptr || c.min_scale == nullptr))
+    return null_argument();
   return GSR_OK;
 }
 
@@ -512,62 +518,46 @@ size_t gsr_sugar_field_workspace_bytes(int M, int K, int N) {
   return field_workspace_bytes(M < 0 ? 0 : M, K, N < 0 ? 0 : N);
 }
 
-int gsr_sugar_field_forward(int M, int K, int N, int R, const float* x, const long long* nbr, const long long* row,
-                            const float* centers, const float* inv_sr, const float* strengths, const float* min_scale,
-                            float density_factor, float* density, float* beta_avg, float* op, void* workspace,
+int gsr_sugar_field_forward(const gsr_sugar_field* in, float* density, float* beta_avg, float* op, void* workspace,
                             size_t workspace_bytes, void* stream) {
-  FieldCall c;
-  if (field_check(M, K, N, R, x, nbr, row, centers, inv_sr, strengths, min_scale, c) != GSR_OK) return GSR_EINVAL;
-  c.density_factor = density_factor;
-  if (M == 0) {  // nothing to launch, no device touched
-    g_err[0] = 0;
-    return GSR_OK;
-  }
-  if (density == nullptr || beta_avg == nullptr || workspace == nullptr)
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
-  if (workspace_bytes < field_workspace_bytes(0, K, N)) return fail(GSR_EINVAL, "%s", "workspace too small");
-  launch_field_forward(c, density, beta_avg, op, workspace, (hipStream_t)stream);
+  if (in == nullptr) return null_argument();
+  if (field_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->M == 0) return nothing_to_do();
+  if (density == nullptr || beta_avg == nullptr || workspace == nullptr) return null_argument();
+  if (workspace_bytes < field_workspace_bytes(0, in->K, in->N)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_field_forward(*in, density, beta_avg, op, workspace, (hipStream_t)stream);
   return last_launch();
 }
 
-int gsr_sugar_field_backward(int M, int K, int N, int R, const float* x, const long long* nbr, const long long* row,
-                             const float* centers, const float* inv_sr, const float* strengths, const float* min_scale,
-                             float density_factor, const float* dL_ddensity, const float* dL_dbeta_avg,
+int gsr_sugar_field_backward(const gsr_sugar_field* in, const float* dL_ddensity, const float* dL_dbeta_avg,
                              const float* dL_dop, float* dL_dx, float* dL_dcenters, float* dL_dinv_sr,
                              float* dL_dstrengths, float* dL_dmin_scale, void* workspace, size_t workspace_bytes,
                              void* stream) {
-  FieldCall c;
-  if (field_check(M, K, N, R, x, nbr, row, centers, inv_sr, strengths, min_scale, c) != GSR_OK) return GSR_EINVAL;
-  c.density_factor = density_factor;
-  if (M == 0) {
-    g_err[0] = 0;
-    return GSR_OK;
-  }
+  if (in == nullptr) return null_argument();
+  if (field_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->M == 0) return nothing_to_do();
   if (dL_dx == nullptr || workspace == nullptr ||
-      (N > 0 && (dL_dcenters == nullptr || dL_dinv_sr == nullptr || dL_dstrengths == nullptr ||
-                 dL_dmin_scale == nullptr)))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
-  if (workspace_bytes < field_workspace_bytes(M, K, N)) return fail(GSR_EINVAL, "%s", "workspace too small");
-  const int e = launch_field_backward(c, dL_ddensity, dL_dbeta_avg, dL_dop, dL_dx, dL_dcenters, dL_dinv_sr,
+      (in->N > 0 && (dL_dcenters == nullptr || dL_dinv_sr == nullptr || dL_dstrengths == nullptr ||
+                     dL_dmin_scale == nullptr)))
+    return null_argument();
+  if (workspace_bytes < field_workspace_bytes(in->M, in->K, in->N))
+    return fail(GSR_EINVAL, "%s", "workspace too small");
+  const int e = launch_field_backward(*in, dL_ddensity, dL_dbeta_avg, dL_dop, dL_dx, dL_dcenters, dL_dinv_sr,
                                       dL_dstrengths, dL_dmin_scale, workspace, (hipStream_t)stream);
   if (e != 0) return fail(GSR_EHIP, "HIP error: %s", hipGetErrorString((hipError_t)e));
   return last_launch();
 }
 
 // ---- the SuGaR neighbour-normal loss (gsr_normal.hip) ----------------------------------------------
-static int normal_check(int M, int K, int N, int R, const float* x, const long long* gaussian_idx,
-                        const long long* nbr, int nbr_per_sample, const float* centers, const float* normals,
-                        const float* min_scale, const float* op, NormalCall& c) {
-  if (K < 1 || K > GSR_KNN_MAX_K) return fail(GSR_EINVAL, "%s", "K must be in 1..32");
-  if (M < 0 || N < 0 || R < 0) return fail(GSR_EINVAL, "%s", "negative size");
-  if ((long long)M * (K + 1) >= (1ll << 31))
+static int normal_check(const gsr_sugar_normal& c) {
+  if (c.K < 1 || c.K > GSR_KNN_MAX_K) return fail(GSR_EINVAL, "%s", "K must be in 1..32");
+  if (c.M < 0 || c.N < 0 || c.R < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if ((long long)c.M * (c.K + 1) >= (1ll << 31))
     return fail(GSR_EINVAL, "%s", "M x (K + 1) must stay below 2^31: split the samples");
-  if (nbr_per_sample && R != M) return fail(GSR_EINVAL, "%s", "a per-sample neighbour table has M rows");
-  if (M > 0 && (x == nullptr || gaussian_idx == nullptr || op == nullptr || (R > 0 && nbr == nullptr)))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
-  if (N > 0 && (centers == nullptr || normals == nullptr || min_scale == nullptr))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
-  c = NormalCall{M, K, N, R, x, gaussian_idx, nbr, nbr_per_sample != 0, centers, normals, min_scale, op};
+  if (c.per_sample && c.R != c.M) return fail(GSR_EINVAL, "%s", "a per-sample neighbour table has M rows");
+  if (c.M > 0 && (c.x == nullptr || c.own == nullptr || c.op == nullptr || (c.R > 0 && c.nbr == nullptr)))
+    return null_argument();
+  if (c.N > 0 && (c.centers == nullptr || c.normals == nullptr || c.min_scale == nullptr)) return null_argument();
   return GSR_OK;
 }
 
@@ -576,118 +566,94 @@ size_t gsr_sugar_normal_workspace_bytes(int M, int K, int N) {
   return normal_workspace_bytes(M < 0 ? 0 : M, K, N < 0 ? 0 : N);
 }
 
-int gsr_sugar_normal_forward(int M, int K, int N, int R, const float* x, const long long* gaussian_idx,
-                             const long long* nbr, int nbr_per_sample, const float* centers, const float* normals,
-                             const float* min_scale, const float* op, float* loss, float* rec, void* workspace,
+int gsr_sugar_normal_forward(const gsr_sugar_normal* in, float* loss, float* rec, void* workspace,
                              size_t workspace_bytes, void* stream) {
-  NormalCall c;
-  if (normal_check(M, K, N, R, x, gaussian_idx, nbr, nbr_per_sample, centers, normals, min_scale, op, c) != GSR_OK)
-    return GSR_EINVAL;
-  if (M == 0) {  // nothing to launch, no device touched
-    g_err[0] = 0;
-    return GSR_OK;
-  }
-  if (loss == nullptr || workspace == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (in == nullptr) return null_argument();
+  if (normal_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->M == 0) return nothing_to_do();
+  if (loss == nullptr || workspace == nullptr) return null_argument();
   if (((uintptr_t)rec & 15u) != 0) return fail(GSR_EINVAL, "%s", "rec must be 16-byte aligned");
-  if (workspace_bytes < normal_workspace_bytes(0, K, N)) return fail(GSR_EINVAL, "%s", "workspace too small");
-  launch_normal_forward(c, loss, rec, workspace, (hipStream_t)stream);
+  if (workspace_bytes < normal_workspace_bytes(0, in->K, in->N)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_normal_forward(*in, loss, rec, workspace, (hipStream_t)stream);
   return last_launch();
 }
 
-int gsr_sugar_normal_backward(int M, int K, int N, int R, const float* x, const long long* gaussian_idx,
-                              const long long* nbr, int nbr_per_sample, const float* centers, const float* normals,
-                              const float* min_scale, const float* op, const float* rec, const float* dL_dloss,
-                              float* dL_dnormals, void* workspace, size_t workspace_bytes, void* stream) {
-  NormalCall c;
-  if (normal_check(M, K, N, R, x, gaussian_idx, nbr, nbr_per_sample, centers, normals, min_scale, op, c) != GSR_OK)
-    return GSR_EINVAL;
-  if (M == 0) {
-    g_err[0] = 0;
-    return GSR_OK;
-  }
-  if (rec == nullptr || dL_dloss == nullptr || workspace == nullptr || (N > 0 && dL_dnormals == nullptr))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
+int gsr_sugar_normal_backward(const gsr_sugar_normal* in, const float* rec, const float* dL_dloss, float* dL_dnormals,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  if (in == nullptr) return null_argument();
+  if (normal_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->M == 0) return nothing_to_do();
+  if (rec == nullptr || dL_dloss == nullptr || workspace == nullptr || (in->N > 0 && dL_dnormals == nullptr))
+    return null_argument();
   if (((uintptr_t)rec & 15u) != 0) return fail(GSR_EINVAL, "%s", "rec must be 16-byte aligned");
-  if (workspace_bytes < normal_workspace_bytes(M, K, N)) return fail(GSR_EINVAL, "%s", "workspace too small");
-  const int e = launch_normal_backward(c, rec, dL_dloss, dL_dnormals, workspace, (hipStream_t)stream);
+  if (workspace_bytes < normal_workspace_bytes(in->M, in->K, in->N))
+    return fail(GSR_EINVAL, "%s", "workspace too small");
+  const int e = launch_normal_backward(*in, rec, dL_dloss, dL_dnormals, workspace, (hipStream_t)stream);
   if (e != 0) return fail(GSR_EHIP, "HIP error: %s", hipGetErrorString((hipError_t)e));
   return last_launch();
 }
 
 // ---- the geometry of mesh-bound SuGaR Gaussians (gsr_mesh.hip) -------------------------------------
-static int mesh_check(int V, int F, int G, int N, const float* verts, const int* faces, const float* bary,
-                      const float* complex_numbers, const float* log_scales, MeshCall& c) {
-  if (G < 1 || G > GSR_MESH_MAX_G) return fail(GSR_EINVAL, "%s", "G must be in 1..8");
-  if (V < 0 || F < 0 || N < 0) return fail(GSR_EINVAL, "%s", "negative size");
-  if ((long long)F * G != (long long)N) return fail(GSR_EINVAL, "%s", "N must equal F x G");
-  if (bary == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
-  if (F > 0 && (faces == nullptr || complex_numbers == nullptr || log_scales == nullptr || (V > 0 && verts == nullptr)))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
-  if ((((uintptr_t)complex_numbers | (uintptr_t)log_scales) & 7u) != 0)
+static int mesh_check(const gsr_sugar_mesh& c, int N, const float* bary) {
+  if (c.G < 1 || c.G > GSR_MESH_MAX_G) return fail(GSR_EINVAL, "%s", "G must be in 1..8");
+  if (c.V < 0 || c.F < 0 || N < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if ((long long)c.F * c.G != (long long)N) return fail(GSR_EINVAL, "%s", "N must equal F x G");
+  if (bary == nullptr) return null_argument();
+  if (c.F > 0 &&
+      (c.faces == nullptr || c.cplx == nullptr || c.log_scales == nullptr || (c.V > 0 && c.verts == nullptr)))
+    return null_argument();
+  if ((((uintptr_t)c.cplx | (uintptr_t)c.log_scales) & 7u) != 0)
     return fail(GSR_EINVAL, "%s", "complex_numbers and log_scales must be 8-byte aligned");
-  c = MeshCall{V, F, G, verts, faces, complex_numbers, log_scales};
   return GSR_OK;
 }
 
 size_t gsr_sugar_mesh_workspace_bytes(int F, int V) { return mesh_workspace_bytes(F < 0 ? 0 : F, V < 0 ? 0 : V); }
 
-int gsr_sugar_mesh_forward(int V, int F, int G, int N, const float* verts, const int* faces, const float* bary,
-                           const float* complex_numbers, const float* log_scales, float thickness, float* xyz,
+int gsr_sugar_mesh_forward(const gsr_sugar_mesh* in, int N, const float* bary, float thickness, float* xyz,
                            float* scaling, float* rotation, float* normals, void* stream) {
-  MeshCall c;
-  if (mesh_check(V, F, G, N, verts, faces, bary, complex_numbers, log_scales, c) != GSR_OK) return GSR_EINVAL;
-  if (F == 0) {  // nothing to launch, no device touched
-    g_err[0] = 0;
-    return GSR_OK;
-  }
-  if (xyz == nullptr || scaling == nullptr || rotation == nullptr || normals == nullptr)
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (in == nullptr) return null_argument();
+  if (mesh_check(*in, N, bary) != GSR_OK) return GSR_EINVAL;
+  if (in->F == 0) return nothing_to_do();
+  if (xyz == nullptr || scaling == nullptr || rotation == nullptr || normals == nullptr) return null_argument();
   if (((uintptr_t)rotation & 15u) != 0) return fail(GSR_EINVAL, "%s", "rotation must be 16-byte aligned");
-  launch_mesh_forward(c, bary, thickness, xyz, scaling, rotation, normals, (hipStream_t)stream);
+  launch_mesh_forward(*in, bary, thickness, xyz, scaling, rotation, normals, (hipStream_t)stream);
   return last_launch();
 }
 
-int gsr_sugar_mesh_backward(int V, int F, int G, int N, const float* verts, const int* faces, const float* bary,
-                            const float* complex_numbers, const float* log_scales, const int* corner_order,
+int gsr_sugar_mesh_backward(const gsr_sugar_mesh* in, int N, const float* bary, const int* corner_order,
                             const int* vert_offsets, const float* dL_dxyz, const float* dL_dscaling,
                             const float* dL_drotation, const float* dL_dnormals, float* dL_dverts, float* dL_dcomplex,
                             float* dL_dlog_scales, void* workspace, size_t workspace_bytes, void* stream) {
-  MeshCall c;
-  if (mesh_check(V, F, G, N, verts, faces, bary, complex_numbers, log_scales, c) != GSR_OK) return GSR_EINVAL;
-  if (F == 0) {
-    g_err[0] = 0;
-    return GSR_OK;
-  }
+  if (in == nullptr) return null_argument();
+  if (mesh_check(*in, N, bary) != GSR_OK) return GSR_EINVAL;
+  if (in->F == 0) return nothing_to_do();
   if (corner_order == nullptr || vert_offsets == nullptr || dL_dcomplex == nullptr || dL_dlog_scales == nullptr ||
-      workspace == nullptr || (V > 0 && dL_dverts == nullptr))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
+      workspace == nullptr || (in->V > 0 && dL_dverts == nullptr))
+    return null_argument();
   if (((uintptr_t)dL_drotation & 15u) != 0) return fail(GSR_EINVAL, "%s", "dL_drotation must be 16-byte aligned");
   if ((((uintptr_t)dL_dcomplex | (uintptr_t)dL_dlog_scales) & 7u) != 0)
     return fail(GSR_EINVAL, "%s", "dL_dcomplex and dL_dlog_scales must be 8-byte aligned");
-  if (workspace_bytes < mesh_workspace_bytes(F, V)) return fail(GSR_EINVAL, "%s", "workspace too small");
-  launch_mesh_backward(c, bary, corner_order, vert_offsets, dL_dxyz, dL_dscaling, dL_drotation, dL_dnormals, dL_dverts,
-                       dL_dcomplex, dL_dlog_scales, workspace, (hipStream_t)stream);
+  if (workspace_bytes < mesh_workspace_bytes(in->F, in->V)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_mesh_backward(*in, bary, corner_order, vert_offsets, dL_dxyz, dL_dscaling, dL_drotation, dL_dnormals,
+                       dL_dverts, dL_dcomplex, dL_dlog_scales, workspace, (hipStream_t)stream);
   return last_launch();
 }
 
 // ---- the time-batched geometry of dynamic SuGaR (gsr_dynamic.hip) ----------------------------------
 static bool below_2_31(long long a, long long b) { return a * b < (1ll << 31); }
 
-static int skin_check(int T, int V, int P, int K, int method, const float* verts, const float* node_xyz,
-                      const float* node_trans, const float* node_rots, const float* node_scales, const int* nbr,
-                      const float* w, SkinCall& c) {
-  if (K < 1 || K > GSR_SKIN_MAX_K) return fail(GSR_EINVAL, "%s", "K must be in 1..32");
-  if (method != GSR_SKIN_DQS && method != GSR_SKIN_LBS)
+static int skin_check(const gsr_sugar_skin& c) {
+  if (c.K < 1 || c.K > GSR_SKIN_MAX_K) return fail(GSR_EINVAL, "%s", "K must be in 1..32");
+  if (c.method != GSR_SKIN_DQS && c.method != GSR_SKIN_LBS)
     return fail(GSR_EINVAL, "%s", "method must be GSR_SKIN_DQS or GSR_SKIN_LBS");
-  if (T < 0 || V < 0 || P < 0) return fail(GSR_EINVAL, "%s", "negative size");
-  if (!below_2_31(T, V) || !below_2_31(T, P) || !below_2_31(V, K))
+  if (c.T < 0 || c.V < 0 || c.P < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if (!below_2_31(c.T, c.V) || !below_2_31(c.T, c.P) || !below_2_31(c.V, c.K))
     return fail(GSR_EINVAL, "%s", "T x V, T x P and V x K must stay below 2^31");
-  if (T > 0 && V > 0 &&
-      (P == 0 || verts == nullptr || node_xyz == nullptr || node_trans == nullptr || node_rots == nullptr ||
-       nbr == nullptr || w == nullptr))
-    return fail(GSR_EINVAL, "%s", P == 0 ? "vertices without nodes" : "null pointer argument");
-  if (((uintptr_t)node_rots & 15u) != 0) return fail(GSR_EINVAL, "%s", "node_rots must be 16-byte aligned");
-  c = SkinCall{T, V, P, K, method, verts, node_xyz, node_trans, node_rots, node_scales, nbr, w};
+  if (c.T > 0 && c.V > 0 &&
+      (c.P == 0 || c.verts == nullptr || c.node_xyz == nullptr || c.node_trans == nullptr || c.node_rots == nullptr ||
+       c.nbr == nullptr || c.w == nullptr))
+    return fail(GSR_EINVAL, "%s", c.P == 0 ? "vertices without nodes" : "null pointer argument");
+  if (((uintptr_t)c.node_rots & 15u) != 0) return fail(GSR_EINVAL, "%s", "node_rots must be 16-byte aligned");
   return GSR_OK;
 }
 
@@ -695,186 +661,147 @@ size_t gsr_sugar_skin_workspace_bytes(int T, int V, int P) {
   return skin_workspace_bytes(T < 0 ? 0 : T, V < 0 ? 0 : V, P < 0 ? 0 : P);
 }
 
-int gsr_sugar_skin_forward(int T, int V, int P, int K, int method, const float* verts, const float* node_xyz,
-                           const float* node_trans, const float* node_rots, const float* node_scales, const int* nbr,
-                           const float* w, float* vert_xyz, float* vert_rot, float* vert_scale, void* workspace,
-                           size_t workspace_bytes, void* stream) {
-  SkinCall c;
-  if (skin_check(T, V, P, K, method, verts, node_xyz, node_trans, node_rots, node_scales, nbr, w, c) != GSR_OK)
-    return GSR_EINVAL;
-  if (T == 0 || V == 0) {  // nothing to launch, no device touched
-    g_err[0] = 0;
-    return GSR_OK;
-  }
+int gsr_sugar_skin_forward(const gsr_sugar_skin* in, float* vert_xyz, float* vert_rot, float* vert_scale,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  if (in == nullptr) return null_argument();
+  if (skin_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->T == 0 || in->V == 0) return nothing_to_do();
   if (vert_xyz == nullptr || vert_rot == nullptr || workspace == nullptr ||
-      (node_scales != nullptr && vert_scale == nullptr))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
+      (in->node_scales != nullptr && vert_scale == nullptr))
+    return null_argument();
   if (((uintptr_t)vert_rot & 15u) != 0) return fail(GSR_EINVAL, "%s", "vert_rot must be 16-byte aligned");
-  if (workspace_bytes < skin_workspace_bytes(T, V, P)) return fail(GSR_EINVAL, "%s", "workspace too small");
-  launch_skin_forward(c, vert_xyz, vert_rot, vert_scale, workspace, (hipStream_t)stream);
+  if (workspace_bytes < skin_workspace_bytes(in->T, in->V, in->P))
+    return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_skin_forward(*in, vert_xyz, vert_rot, vert_scale, workspace, (hipStream_t)stream);
   return last_launch();
 }
 
-int gsr_sugar_skin_backward(int T, int V, int P, int K, int method, const float* verts, const float* node_xyz,
-                            const float* node_trans, const float* node_rots, const float* node_scales, const int* nbr,
-                            const float* w, const int* item_order, const int* node_offsets, const float* dL_dxyz,
-                            const float* dL_drot, const float* dL_dscale, float* dL_dverts, float* dL_dnode_trans,
-                            float* dL_dnode_rots, float* dL_dnode_scales, void* workspace, size_t workspace_bytes,
-                            void* stream) {
-  SkinCall c;
-  if (skin_check(T, V, P, K, method, verts, node_xyz, node_trans, node_rots, node_scales, nbr, w, c) != GSR_OK)
-    return GSR_EINVAL;
-  if (T == 0 || V == 0) {
-    g_err[0] = 0;
-    return GSR_OK;
-  }
+int gsr_sugar_skin_backward(const gsr_sugar_skin* in, const int* item_order, const int* node_offsets,
+                            const float* dL_dxyz, const float* dL_drot, const float* dL_dscale, float* dL_dverts,
+                            float* dL_dnode_trans, float* dL_dnode_rots, float* dL_dnode_scales, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  if (in == nullptr) return null_argument();
+  if (skin_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->T == 0 || in->V == 0) return nothing_to_do();
   if (item_order == nullptr || node_offsets == nullptr || dL_dverts == nullptr || dL_dnode_trans == nullptr ||
-      dL_dnode_rots == nullptr || workspace == nullptr || (node_scales != nullptr && dL_dnode_scales == nullptr))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
+      dL_dnode_rots == nullptr || workspace == nullptr || (in->node_scales != nullptr && dL_dnode_scales == nullptr))
+    return null_argument();
   if ((((uintptr_t)dL_drot | (uintptr_t)dL_dnode_rots) & 15u) != 0)
     return fail(GSR_EINVAL, "%s", "dL_drot and dL_dnode_rots must be 16-byte aligned");
-  if (workspace_bytes < skin_workspace_bytes(T, V, P)) return fail(GSR_EINVAL, "%s", "workspace too small");
-  launch_skin_backward(c, item_order, node_offsets, dL_dxyz, dL_drot, node_scales != nullptr ? dL_dscale : nullptr,
-                       dL_dverts, dL_dnode_trans, dL_dnode_rots, dL_dnode_scales, workspace, (hipStream_t)stream);
+  if (workspace_bytes < skin_workspace_bytes(in->T, in->V, in->P))
+    return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_skin_backward(*in, item_order, node_offsets, dL_dxyz, dL_drot,
+                       in->node_scales != nullptr ? dL_dscale : nullptr, dL_dverts, dL_dnode_trans, dL_dnode_rots,
+                       dL_dnode_scales, workspace, (hipStream_t)stream);
   return last_launch();
 }
 
-static int timed_check(int T, int V, int F, int G, int N, const float* vert_xyz, const float* vert_rot,
-                       const float* rotation0, const int* faces, const float* bary, const float* vert_scale,
-                       const float* log_scales, float thickness, TimedCall& c) {
-  if (G < 1 || G > GSR_MESH_MAX_G) return fail(GSR_EINVAL, "%s", "G must be in 1..8");
-  if (T < 0 || V < 0 || F < 0 || N < 0) return fail(GSR_EINVAL, "%s", "negative size");
-  if ((long long)F * G != (long long)N) return fail(GSR_EINVAL, "%s", "N must equal F x G");
-  if (!below_2_31(T, N) || !below_2_31(T, V)) return fail(GSR_EINVAL, "%s", "T x N and T x V must stay below 2^31");
-  if (bary == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
-  if ((vert_scale == nullptr) != (log_scales == nullptr))
+static int timed_check(const gsr_sugar_timed& c, int N, const float* bary) {
+  if (c.G < 1 || c.G > GSR_MESH_MAX_G) return fail(GSR_EINVAL, "%s", "G must be in 1..8");
+  if (c.T < 0 || c.V < 0 || c.F < 0 || N < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if ((long long)c.F * c.G != (long long)N) return fail(GSR_EINVAL, "%s", "N must equal F x G");
+  if (!below_2_31(c.T, N) || !below_2_31(c.T, c.V))
+    return fail(GSR_EINVAL, "%s", "T x N and T x V must stay below 2^31");
+  if (bary == nullptr) return null_argument();
+  if ((c.vert_scale == nullptr) != (c.log_scales == nullptr))
     return fail(GSR_EINVAL, "%s", "vert_scale and log_scales are given together or not at all");
-  if (T > 0 && F > 0 &&
-      (faces == nullptr || rotation0 == nullptr || (V > 0 && (vert_xyz == nullptr || vert_rot == nullptr))))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
-  if ((((uintptr_t)vert_rot | (uintptr_t)rotation0) & 15u) != 0)
+  if (c.T > 0 && c.F > 0 &&
+      (c.faces == nullptr || c.rotation0 == nullptr || (c.V > 0 && (c.vert_xyz == nullptr || c.vert_rot == nullptr))))
+    return null_argument();
+  if ((((uintptr_t)c.vert_rot | (uintptr_t)c.rotation0) & 15u) != 0)
     return fail(GSR_EINVAL, "%s", "vert_rot and rotation0 must be 16-byte aligned");
-  if (((uintptr_t)log_scales & 7u) != 0) return fail(GSR_EINVAL, "%s", "log_scales must be 8-byte aligned");
-  c = TimedCall{T, V, F, G, vert_xyz, vert_rot, rotation0, vert_scale, log_scales, faces, thickness};
+  if (((uintptr_t)c.log_scales & 7u) != 0) return fail(GSR_EINVAL, "%s", "log_scales must be 8-byte aligned");
   return GSR_OK;
 }
 
 size_t gsr_sugar_timed_workspace_bytes(int T, int F) { return timed_workspace_bytes(T < 0 ? 0 : T, F < 0 ? 0 : F); }
 
-int gsr_sugar_timed_forward(int T, int V, int F, int G, int N, const float* vert_xyz, const float* vert_rot,
-                            const float* rotation0, const int* faces, const float* bary, const float* vert_scale,
-                            const float* log_scales, float thickness, float* xyz, float* rotation, float* normals,
-                            float* scaling, void* stream) {
-  TimedCall c;
-  if (timed_check(T, V, F, G, N, vert_xyz, vert_rot, rotation0, faces, bary, vert_scale, log_scales, thickness, c) !=
-      GSR_OK)
-    return GSR_EINVAL;
-  if (T == 0 || F == 0) {  // nothing to launch, no device touched
-    g_err[0] = 0;
-    return GSR_OK;
-  }
-  if (xyz == nullptr || rotation == nullptr || normals == nullptr || (vert_scale != nullptr && scaling == nullptr))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
+int gsr_sugar_timed_forward(const gsr_sugar_timed* in, int N, const float* bary, float* xyz, float* rotation,
+                            float* normals, float* scaling, void* stream) {
+  if (in == nullptr) return null_argument();
+  if (timed_check(*in, N, bary) != GSR_OK) return GSR_EINVAL;
+  if (in->T == 0 || in->F == 0) return nothing_to_do();
+  if (xyz == nullptr || rotation == nullptr || normals == nullptr || (in->vert_scale != nullptr && scaling == nullptr))
+    return null_argument();
   if (((uintptr_t)rotation & 15u) != 0) return fail(GSR_EINVAL, "%s", "rotation must be 16-byte aligned");
-  launch_timed_forward(c, bary, xyz, rotation, normals, scaling, (hipStream_t)stream);
+  launch_timed_forward(*in, bary, xyz, rotation, normals, scaling, (hipStream_t)stream);
   return last_launch();
 }
 
-int gsr_sugar_timed_backward(int T, int V, int F, int G, int N, const float* vert_xyz, const float* vert_rot,
-                             const float* rotation0, const int* faces, const float* bary, const float* vert_scale,
-                             const float* log_scales, float thickness, const int* corner_order,
+int gsr_sugar_timed_backward(const gsr_sugar_timed* in, int N, const float* bary, const int* corner_order,
                              const int* vert_offsets, const float* dL_dxyz, const float* dL_drotation,
                              const float* dL_dnormals, const float* dL_dscaling, float* dL_dvert_xyz,
                              float* dL_dvert_rot, float* dL_drotation0, float* dL_dvert_scale, float* dL_dlog_scales,
                              void* workspace, size_t workspace_bytes, void* stream) {
-  TimedCall c;
-  if (timed_check(T, V, F, G, N, vert_xyz, vert_rot, rotation0, faces, bary, vert_scale, log_scales, thickness, c) !=
-      GSR_OK)
-    return GSR_EINVAL;
-  if (T == 0 || F == 0) {
-    g_err[0] = 0;
-    return GSR_OK;
-  }
+  if (in == nullptr) return null_argument();
+  if (timed_check(*in, N, bary) != GSR_OK) return GSR_EINVAL;
+  if (in->T == 0 || in->F == 0) return nothing_to_do();
+  const bool scaled = in->vert_scale != nullptr;
   if (corner_order == nullptr || vert_offsets == nullptr || dL_drotation0 == nullptr || workspace == nullptr ||
-      (V > 0 && (dL_dvert_xyz == nullptr || dL_dvert_rot == nullptr)) ||
-      (vert_scale != nullptr && (dL_dlog_scales == nullptr || (V > 0 && dL_dvert_scale == nullptr))))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
+      (in->V > 0 && (dL_dvert_xyz == nullptr || dL_dvert_rot == nullptr)) ||
+      (scaled && (dL_dlog_scales == nullptr || (in->V > 0 && dL_dvert_scale == nullptr))))
+    return null_argument();
   if ((((uintptr_t)dL_drotation | (uintptr_t)dL_dvert_rot | (uintptr_t)dL_drotation0) & 15u) != 0)
     return fail(GSR_EINVAL, "%s", "dL_drotation, dL_dvert_rot and dL_drotation0 must be 16-byte aligned");
   if (((uintptr_t)dL_dlog_scales & 7u) != 0) return fail(GSR_EINVAL, "%s", "dL_dlog_scales must be 8-byte aligned");
-  if (workspace_bytes < timed_workspace_bytes(T, F)) return fail(GSR_EINVAL, "%s", "workspace too small");
-  launch_timed_backward(c, bary, corner_order, vert_offsets, dL_dxyz, dL_drotation, dL_dnormals,
-                        vert_scale != nullptr ? dL_dscaling : nullptr, dL_dvert_xyz, dL_dvert_rot, dL_drotation0,
-                        dL_dvert_scale, dL_dlog_scales, workspace, (hipStream_t)stream);
+  if (workspace_bytes < timed_workspace_bytes(in->T, in->F)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_timed_backward(*in, bary, corner_order, vert_offsets, dL_dxyz, dL_drotation, dL_dnormals,
+                        scaled ? dL_dscaling : nullptr, dL_dvert_xyz, dL_dvert_rot, dL_drotation0, dL_dvert_scale,
+                        dL_dlog_scales, workspace, (hipStream_t)stream);
   return last_launch();
 }
 
 // ---- the ARAP energy of the deformed mesh (gsr_arap.hip) --------------------------------------------
-static int arap_check(int T, int V, int E, int rot_form, const float* verts, const int* offsets, const int* nbr,
-                      const float* w, const float* vert_xyz, const float* vert_rot, ArapCall& c) {
-  if (rot_form != GSR_ARAP_QUAT && rot_form != GSR_ARAP_MATRIX)
+static int arap_check(const gsr_sugar_arap& c) {
+  if (c.rot_form != GSR_ARAP_QUAT && c.rot_form != GSR_ARAP_MATRIX)
     return fail(GSR_EINVAL, "%s", "rot_form must be GSR_ARAP_QUAT or GSR_ARAP_MATRIX");
-  if (T < 0 || V < 0 || E < 0) return fail(GSR_EINVAL, "%s", "negative size");
-  if (!below_2_31(T, V)) return fail(GSR_EINVAL, "%s", "T x V must stay below 2^31");
-  if (T > 0 && V > 0 &&
-      (verts == nullptr || offsets == nullptr || vert_xyz == nullptr || vert_rot == nullptr ||
-       (E > 0 && (nbr == nullptr || w == nullptr))))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
-  if (rot_form == GSR_ARAP_QUAT && ((uintptr_t)vert_rot & 15u) != 0)
+  if (c.T < 0 || c.V < 0 || c.E < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if (!below_2_31(c.T, c.V)) return fail(GSR_EINVAL, "%s", "T x V must stay below 2^31");
+  if (c.T > 0 && c.V > 0 &&
+      (c.verts == nullptr || c.offsets == nullptr || c.vert_xyz == nullptr || c.vert_rot == nullptr ||
+       (c.E > 0 && (c.nbr == nullptr || c.w == nullptr))))
+    return null_argument();
+  if (c.rot_form == GSR_ARAP_QUAT && ((uintptr_t)c.vert_rot & 15u) != 0)
     return fail(GSR_EINVAL, "%s", "vert_rot must be 16-byte aligned");
-  c = ArapCall{T, V, E, rot_form, verts, w, vert_xyz, vert_rot, offsets, nbr};
   return GSR_OK;
 }
 
 size_t gsr_sugar_arap_workspace_bytes(int T, int V) { return arap_workspace_bytes(T < 0 ? 0 : T, V < 0 ? 0 : V); }
 
-int gsr_sugar_arap_forward(int T, int V, int E, int rot_form, const float* verts, const int* offsets, const int* nbr,
-                           const float* w, const float* vert_xyz, const float* vert_rot, float* energy,
-                           void* workspace, size_t workspace_bytes, void* stream) {
-  ArapCall c;
-  if (arap_check(T, V, E, rot_form, verts, offsets, nbr, w, vert_xyz, vert_rot, c) != GSR_OK) return GSR_EINVAL;
-  if (T == 0 || V == 0) {  // nothing to launch, no device touched
-    g_err[0] = 0;
-    return GSR_OK;
-  }
-  if (energy == nullptr || workspace == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
-  if (workspace_bytes < arap_workspace_bytes(T, V)) return fail(GSR_EINVAL, "%s", "workspace too small");
-  launch_arap_forward(c, energy, workspace, (hipStream_t)stream);
+int gsr_sugar_arap_forward(const gsr_sugar_arap* in, float* energy, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  if (in == nullptr) return null_argument();
+  if (arap_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->T == 0 || in->V == 0) return nothing_to_do();
+  if (energy == nullptr || workspace == nullptr) return null_argument();
+  if (workspace_bytes < arap_workspace_bytes(in->T, in->V)) return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_arap_forward(*in, energy, workspace, (hipStream_t)stream);
   return last_launch();
 }
 
-int gsr_sugar_arap_backward(int T, int V, int E, int rot_form, const float* verts, const int* offsets, const int* nbr,
-                            const float* w, const float* vert_xyz, const float* vert_rot, const float* dL_denergy,
-                            float* dL_dvert_xyz, float* dL_dvert_rot, void* stream) {
-  ArapCall c;
-  if (arap_check(T, V, E, rot_form, verts, offsets, nbr, w, vert_xyz, vert_rot, c) != GSR_OK) return GSR_EINVAL;
-  if (T == 0 || V == 0) {
-    g_err[0] = 0;
-    return GSR_OK;
-  }
-  if (dL_denergy == nullptr || dL_dvert_xyz == nullptr || dL_dvert_rot == nullptr)
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
-  if (rot_form == GSR_ARAP_QUAT && ((uintptr_t)dL_dvert_rot & 15u) != 0)
+int gsr_sugar_arap_backward(const gsr_sugar_arap* in, const float* dL_denergy, float* dL_dvert_xyz,
+                            float* dL_dvert_rot, void* stream) {
+  if (in == nullptr) return null_argument();
+  if (arap_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->T == 0 || in->V == 0) return nothing_to_do();
+  if (dL_denergy == nullptr || dL_dvert_xyz == nullptr || dL_dvert_rot == nullptr) return null_argument();
+  if (in->rot_form == GSR_ARAP_QUAT && ((uintptr_t)dL_dvert_rot & 15u) != 0)
     return fail(GSR_EINVAL, "%s", "dL_dvert_rot must be 16-byte aligned");
-  launch_arap_backward(c, dL_denergy, dL_dvert_xyz, dL_dvert_rot, (hipStream_t)stream);
+  launch_arap_backward(*in, dL_denergy, dL_dvert_xyz, dL_dvert_rot, (hipStream_t)stream);
   return last_launch();
 }
 
 // ---- the B-spline of the timed node attributes (gsr_spline.hip) -------------------------------------
-static int spline_check(int T, int P, int n_knots, int degree, float start_time, float interval, float t_lo,
-                        float t_hi, const float* timestamps, const float* knots_xyz, const float* knots_rot,
-                        const float* knots_scale, SplineCall& c) {
-  if (degree != 1 && degree != 3) return fail(GSR_EINVAL, "%s", "degree must be 1 or 3");
-  if (n_knots < degree + 1) return fail(GSR_EINVAL, "%s", "n_knots must be at least degree + 1");
-  if (T < 0 || P < 0) return fail(GSR_EINVAL, "%s", "negative size");
-  if (!(interval > 0.0f)) return fail(GSR_EINVAL, "%s", "interval must be positive");
-  if (!below_2_31(T, P) || !below_2_31(n_knots, P))
+static int spline_check(const gsr_sugar_spline& c) {
+  if (c.degree != 1 && c.degree != 3) return fail(GSR_EINVAL, "%s", "degree must be 1 or 3");
+  if (c.n_knots < c.degree + 1) return fail(GSR_EINVAL, "%s", "n_knots must be at least degree + 1");
+  if (c.T < 0 || c.P < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if (!(c.interval > 0.0f)) return fail(GSR_EINVAL, "%s", "interval must be positive");
+  if (!below_2_31(c.T, c.P) || !below_2_31(c.n_knots, c.P))
     return fail(GSR_EINVAL, "%s", "T x P and n_knots x P must stay below 2^31");
-  if (T > 0 && P > 0 && (timestamps == nullptr || knots_xyz == nullptr || knots_rot == nullptr))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
-  if (((uintptr_t)knots_rot & 15u) != 0) return fail(GSR_EINVAL, "%s", "knots_rot must be 16-byte aligned");
-  c = SplineCall{T, P, n_knots, degree, start_time, interval, t_lo, t_hi, timestamps, knots_xyz, knots_rot,
-                 knots_scale};
+  if (c.T > 0 && c.P > 0 && (c.timestamps == nullptr || c.knots_xyz == nullptr || c.knots_rot == nullptr))
+    return null_argument();
+  if (((uintptr_t)c.knots_rot & 15u) != 0) return fail(GSR_EINVAL, "%s", "knots_rot must be 16-byte aligned");
   return GSR_OK;
 }
 
@@ -882,45 +809,31 @@ size_t gsr_sugar_spline_workspace_bytes(int T, int P, int degree) {
   return spline_workspace_bytes(T < 0 ? 0 : T, P < 0 ? 0 : P, degree);
 }
 
-int gsr_sugar_spline_forward(int T, int P, int n_knots, int degree, float start_time, float interval, float t_lo,
-                             float t_hi, const float* timestamps, const float* knots_xyz, const float* knots_rot,
-                             const float* knots_scale, float* xyz, float* rot, float* scale, void* stream) {
-  SplineCall c;
-  if (spline_check(T, P, n_knots, degree, start_time, interval, t_lo, t_hi, timestamps, knots_xyz, knots_rot,
-                   knots_scale, c) != GSR_OK)
-    return GSR_EINVAL;
-  if (T == 0 || P == 0) {  // nothing to launch, no device touched
-    g_err[0] = 0;
-    return GSR_OK;
-  }
-  if (xyz == nullptr || rot == nullptr || (knots_scale != nullptr && scale == nullptr))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
+int gsr_sugar_spline_forward(const gsr_sugar_spline* in, float* xyz, float* rot, float* scale, void* stream) {
+  if (in == nullptr) return null_argument();
+  if (spline_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->T == 0 || in->P == 0) return nothing_to_do();
+  if (xyz == nullptr || rot == nullptr || (in->knots_scale != nullptr && scale == nullptr)) return null_argument();
   if (((uintptr_t)rot & 15u) != 0) return fail(GSR_EINVAL, "%s", "rot must be 16-byte aligned");
-  launch_spline_forward(c, xyz, rot, scale, (hipStream_t)stream);
+  launch_spline_forward(*in, xyz, rot, scale, (hipStream_t)stream);
   return last_launch();
 }
 
-int gsr_sugar_spline_backward(int T, int P, int n_knots, int degree, float start_time, float interval, float t_lo,
-                              float t_hi, const float* timestamps, const float* knots_xyz, const float* knots_rot,
-                              const float* knots_scale, const float* dL_dxyz, const float* dL_drot,
+int gsr_sugar_spline_backward(const gsr_sugar_spline* in, const float* dL_dxyz, const float* dL_drot,
                               const float* dL_dscale, float* dL_dknots_xyz, float* dL_dknots_rot,
                               float* dL_dknots_scale, void* workspace, size_t workspace_bytes, void* stream) {
-  SplineCall c;
-  if (spline_check(T, P, n_knots, degree, start_time, interval, t_lo, t_hi, timestamps, knots_xyz, knots_rot,
-                   knots_scale, c) != GSR_OK)
-    return GSR_EINVAL;
-  if (T == 0 || P == 0) {
-    g_err[0] = 0;
-    return GSR_OK;
-  }
+  if (in == nullptr) return null_argument();
+  if (spline_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->T == 0 || in->P == 0) return nothing_to_do();
   if (dL_dknots_xyz == nullptr || dL_dknots_rot == nullptr || workspace == nullptr ||
-      (knots_scale != nullptr && dL_dknots_scale == nullptr))
-    return fail(GSR_EINVAL, "%s", "null pointer argument");
+      (in->knots_scale != nullptr && dL_dknots_scale == nullptr))
+    return null_argument();
   if ((((uintptr_t)dL_drot | (uintptr_t)dL_dknots_rot) & 15u) != 0)
     return fail(GSR_EINVAL, "%s", "dL_drot and dL_dknots_rot must be 16-byte aligned");
   if (((uintptr_t)workspace & 7u) != 0) return fail(GSR_EINVAL, "%s", "workspace must be 8-byte aligned");
-  if (workspace_bytes < spline_workspace_bytes(T, P, degree)) return fail(GSR_EINVAL, "%s", "workspace too small");
-  launch_spline_backward(c, dL_dxyz, dL_drot, dL_dscale, dL_dknots_xyz, dL_dknots_rot, dL_dknots_scale, workspace,
+  if (workspace_bytes < spline_workspace_bytes(in->T, in->P, in->degree))
+    return fail(GSR_EINVAL, "%s", "workspace too small");
+  launch_spline_backward(*in, dL_dxyz, dL_drot, dL_dscale, dL_dknots_xyz, dL_dknots_rot, dL_dknots_scale, workspace,
                          (hipStream_t)stream);
   return last_launch();
 }

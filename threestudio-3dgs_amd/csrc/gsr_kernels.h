@@ -2,6 +2,7 @@
 // include/gsr.h).  All launchers enqueue on `stream` and never synchronise.
 #pragma once
 
+#include "../../include/gsr.h"
 #include "gsr_common.h"
 
 namespace gsr {
@@ -254,13 +255,7 @@ int launch_knn_points(int P, int K, const float* points, float* dists, long long
 // The SuGaR neighbour density field (include/gsr.h gsr_sugar_field_*) — gsr_field.hip.  M samples, K neighbour slots,
 // N Gaussians, nbr (R, K); row (M,) or null (then R = M).  The forward uses the first field_workspace_bytes(0, K, N)
 // bytes of the workspace only.
-struct FieldCall {
-  int M, K, N, R;
-  const float* x;
-  const long long *nbr, *row;
-  const float *centers, *inv_sr, *strengths, *min_scale;
-  float density_factor;
-};
+using FieldCall = gsr_sugar_field;
 size_t field_workspace_bytes(long long M, int K, int N);
 // lanes per Gaussian of the backward's per-Gaussian sums (64 or 16: part of the documented sum order)
 int field_gauss_lanes(long long M, int K, int N);
@@ -273,13 +268,7 @@ int launch_field_backward(const FieldCall& c, const float* g_density, const floa
 // The SuGaR neighbour-normal loss (include/gsr.h gsr_sugar_normal_*) — gsr_normal.hip.  own (M,) is each sample's
 // Gaussian; nbr (R, K) is read at row m (per_sample, R = M) or at row own[m].  The forward uses the first
 // normal_workspace_bytes(0, K, N) bytes of the workspace only; rec is the forward's (M, 4) record (r, Wc).
-struct NormalCall {
-  int M, K, N, R;
-  const float* x;
-  const long long *own, *nbr;
-  int per_sample;
-  const float *centers, *normals, *min_scale, *op;
-};
+using NormalCall = gsr_sugar_normal;
 size_t normal_workspace_bytes(long long M, int K, int N);
 // lanes per Gaussian of the backward's per-Gaussian sums (64 or 16: part of the documented sum order)
 int normal_gauss_lanes(long long M, int K, int N);
@@ -290,12 +279,7 @@ int launch_normal_backward(const NormalCall& c, const float* rec, const float* g
 // The geometry of mesh-bound SuGaR Gaussians (include/gsr.h gsr_sugar_mesh_*) — gsr_mesh.hip.  V vertices, F faces,
 // G Gaussians per face; cplx and log_scales are (F G, 2).  bary (G, 3) is host memory.  The backward's workspace
 // holds the (3 F, 3) corner rows.
-struct MeshCall {
-  int V, F, G;
-  const float* verts;
-  const int* faces;
-  const float *cplx, *log_scales;
-};
+using MeshCall = gsr_sugar_mesh;
 size_t mesh_workspace_bytes(int F, int V);
 void launch_mesh_forward(const MeshCall& c, const float* bary, float thickness, float* xyz, float* scaling,
                          float* rotation, float* normals, hipStream_t stream);
@@ -305,12 +289,7 @@ void launch_mesh_backward(const MeshCall& c, const float* bary, const int* corne
 // The time-batched geometry of dynamic SuGaR (include/gsr.h gsr_sugar_skin_*, gsr_sugar_timed_*) — gsr_dynamic.hip.
 // Skinning: T frames, V vertices, P nodes, K nodes per vertex; node_scales may be null.  The workspace holds the
 // per-(t, node) records (forward and backward) and, for the backward, the (T V) adjoint rows and dL/dverts terms.
-struct SkinCall {
-  int T, V, P, K, method;  // GSR_SKIN_DQS or GSR_SKIN_LBS
-  const float *verts, *node_xyz, *node_trans, *node_rots, *node_scales;
-  const int* nbr;
-  const float* w;
-};
+using SkinCall = gsr_sugar_skin;
 size_t skin_workspace_bytes(int T, int V, int P);
 void launch_skin_forward(const SkinCall& c, float* xyz, float* rot, float* scale, void* workspace, hipStream_t stream);
 void launch_skin_backward(const SkinCall& c, const int* item_order, const int* node_offsets, const float* g_xyz,
@@ -318,12 +297,7 @@ void launch_skin_backward(const SkinCall& c, const int* item_order, const int* n
                           float* dscales, void* workspace, hipStream_t stream);
 // Timed Gaussians: F faces, G Gaussians per face; vert_scale and log_scales are both given or both null.  bary (G, 3)
 // is host memory.  The backward's workspace holds the (T, 3 F, 10) corner rows.
-struct TimedCall {
-  int T, V, F, G;
-  const float *vert_xyz, *vert_rot, *rotation0, *vert_scale, *log_scales;
-  const int* faces;
-  float thickness;
-};
+using TimedCall = gsr_sugar_timed;
 size_t timed_workspace_bytes(int T, int F);
 void launch_timed_forward(const TimedCall& c, const float* bary, float* xyz, float* rotation, float* normals,
                           float* scaling, hipStream_t stream);
@@ -334,22 +308,14 @@ void launch_timed_backward(const TimedCall& c, const float* bary, const int* cor
 // The as-rigid-as-possible energy of the deformed mesh (include/gsr.h gsr_sugar_arap_*) — gsr_arap.hip.  T frames, V
 // vertices, E directed one-ring edges in CSR (offsets (V+1,), nbr and w (E,)); verts: the rest vertices; vert_rot
 // (T, V, 4) xyzw or (T, V, 3, 3) by rot_form.  The forward's workspace holds one fp64 partial sum per block.
-struct ArapCall {
-  int T, V, E, rot_form;  // GSR_ARAP_QUAT or GSR_ARAP_MATRIX
-  const float *verts, *w, *vert_xyz, *vert_rot;
-  const int *offsets, *nbr;
-};
+using ArapCall = gsr_sugar_arap;
 size_t arap_workspace_bytes(int T, int V);
 void launch_arap_forward(const ArapCall& c, float* energy, void* workspace, hipStream_t stream);
 void launch_arap_backward(const ArapCall& c, const float* g_energy, float* dxyz, float* drot, hipStream_t stream);
 // The B-spline of the timed node attributes (include/gsr.h gsr_sugar_spline_*) — gsr_spline.hip.  T timestamps, P
 // points, n_knots frame-major knots of degree 1 or 3; knots_scale may be null.  The backward's workspace holds the
 // (T, degree + 1, 10, P) fp64 gradient rows.
-struct SplineCall {
-  int T, P, n_knots, degree;
-  float start, interval, lo, hi;  // the grid and the clamp bounds, fp32
-  const float *timestamps, *knots_xyz, *knots_rot, *knots_scale;
-};
+using SplineCall = gsr_sugar_spline;
 size_t spline_workspace_bytes(int T, int P, int degree);
 void launch_spline_forward(const SplineCall& c, float* xyz, float* rot, float* scale, hipStream_t stream);
 void launch_spline_backward(const SplineCall& c, const float* g_xyz, const float* g_rot, const float* g_scale,

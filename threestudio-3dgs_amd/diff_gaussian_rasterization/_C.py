@@ -62,8 +62,44 @@ class SetGrads(ctypes.Structure):
                 + [("accumulate", _i), ("work", _vp), ("work_bytes", _sz), ("n_chunks", _i), ("chunk_events", _vpp)])
 
 
+# The inputs of the fused SuGaR stages (gsr_sugar_*_forward / _backward take one as their first argument).
+class SugarField(ctypes.Structure):
+    _fields_ = (_fields(_i, "M K N R") + _fields(_vp, "x nbr row centers inv_sr strengths min_scale")
+                + [("density_factor", _f)])
+
+
+class SugarNormal(ctypes.Structure):
+    _fields_ = (_fields(_i, "M K N R") + _fields(_vp, "x own nbr") + [("per_sample", _i)]
+                + _fields(_vp, "centers normals min_scale op"))
+
+
+class SugarMesh(ctypes.Structure):
+    _fields_ = _fields(_i, "V F G") + _fields(_vp, "verts faces cplx log_scales")
+
+
+class SugarSkin(ctypes.Structure):
+    _fields_ = (_fields(_i, "T V P K method")
+                + _fields(_vp, "verts node_xyz node_trans node_rots node_scales nbr w"))
+
+
+class SugarTimed(ctypes.Structure):
+    _fields_ = (_fields(_i, "T V F G") + _fields(_vp, "vert_xyz vert_rot rotation0 vert_scale log_scales faces")
+                + [("thickness", _f)])
+
+
+class SugarArap(ctypes.Structure):
+    _fields_ = _fields(_i, "T V E rot_form") + _fields(_vp, "verts w vert_xyz vert_rot offsets nbr")
+
+
+class SugarSpline(ctypes.Structure):
+    _fields_ = (_fields(_i, "T P n_knots degree") + _fields(_f, "start interval lo hi")
+                + _fields(_vp, "timestamps knots_xyz knots_rot knots_scale"))
+
+
 STRUCTS = {"gsr_set_scene": SetScene, "gsr_set_state": SetState, "gsr_set_outputs": SetOutputs,
-           "gsr_set_grads": SetGrads}
+           "gsr_set_grads": SetGrads, "gsr_sugar_field": SugarField, "gsr_sugar_normal": SugarNormal,
+           "gsr_sugar_mesh": SugarMesh, "gsr_sugar_skin": SugarSkin, "gsr_sugar_timed": SugarTimed,
+           "gsr_sugar_arap": SugarArap, "gsr_sugar_spline": SugarSpline}
 
 # name -> (restype, argtypes); must match include/gsr.h exactly (checked by tests/test_abi.py)
 SIGNATURES = {
@@ -104,26 +140,27 @@ SIGNATURES = {
     "gsr_knn_points_workspace_bytes": (_sz, [_i, _i]),
     "gsr_knn_points": (_i, [_i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gsr_sugar_field_workspace_bytes": (_sz, [_i, _i, _i]),
-    "gsr_sugar_field_forward": (_i, [_i, _i, _i, _i] + [_vp] * 7 + [_f] + [_vp] * 4 + [_sz, _vp]),
-    "gsr_sugar_field_backward": (_i, [_i, _i, _i, _i] + [_vp] * 7 + [_f] + [_vp] * 9 + [_sz, _vp]),
+    # (after the struct: [N, bary, thickness], the backward's tables, upstream gradients, outputs, workspace, stream)
+    "gsr_sugar_field_forward": (_i, [_P(SugarField)] + [_vp] * 3 + [_vp, _sz, _vp]),
+    "gsr_sugar_field_backward": (_i, [_P(SugarField)] + [_vp] * 3 + [_vp] * 5 + [_vp, _sz, _vp]),
     "gsr_sugar_normal_workspace_bytes": (_sz, [_i, _i, _i]),
-    "gsr_sugar_normal_forward": (_i, [_i, _i, _i, _i] + [_vp] * 3 + [_i] + [_vp] * 7 + [_sz, _vp]),
-    "gsr_sugar_normal_backward": (_i, [_i, _i, _i, _i] + [_vp] * 3 + [_i] + [_vp] * 8 + [_sz, _vp]),
+    "gsr_sugar_normal_forward": (_i, [_P(SugarNormal)] + [_vp] * 2 + [_vp, _sz, _vp]),
+    "gsr_sugar_normal_backward": (_i, [_P(SugarNormal)] + [_vp] * 2 + [_vp] + [_vp, _sz, _vp]),
     "gsr_sugar_mesh_workspace_bytes": (_sz, [_i, _i]),
-    "gsr_sugar_mesh_forward": (_i, [_i, _i, _i, _i] + [_vp] * 5 + [_f] + [_vp] * 4 + [_vp]),
-    "gsr_sugar_mesh_backward": (_i, [_i, _i, _i, _i] + [_vp] * 5 + [_vp] * 2 + [_vp] * 4 + [_vp] * 3 + [_vp, _sz, _vp]),
+    "gsr_sugar_mesh_forward": (_i, [_P(SugarMesh), _i, _vp, _f] + [_vp] * 4 + [_vp]),
+    "gsr_sugar_mesh_backward": (_i, [_P(SugarMesh), _i, _vp] + [_vp] * 2 + [_vp] * 4 + [_vp] * 3 + [_vp, _sz, _vp]),
     "gsr_sugar_skin_workspace_bytes": (_sz, [_i, _i, _i]),
-    "gsr_sugar_skin_forward": (_i, [_i] * 5 + [_vp] * 7 + [_vp] * 3 + [_vp, _sz, _vp]),
-    "gsr_sugar_skin_backward": (_i, [_i] * 5 + [_vp] * 7 + [_vp] * 2 + [_vp] * 3 + [_vp] * 4 + [_vp, _sz, _vp]),
+    "gsr_sugar_skin_forward": (_i, [_P(SugarSkin)] + [_vp] * 3 + [_vp, _sz, _vp]),
+    "gsr_sugar_skin_backward": (_i, [_P(SugarSkin)] + [_vp] * 2 + [_vp] * 3 + [_vp] * 4 + [_vp, _sz, _vp]),
     "gsr_sugar_timed_workspace_bytes": (_sz, [_i, _i]),
-    "gsr_sugar_timed_forward": (_i, [_i] * 5 + [_vp] * 7 + [_f] + [_vp] * 4 + [_vp]),
-    "gsr_sugar_timed_backward": (_i, [_i] * 5 + [_vp] * 7 + [_f] + [_vp] * 2 + [_vp] * 4 + [_vp] * 5 + [_vp, _sz, _vp]),
+    "gsr_sugar_timed_forward": (_i, [_P(SugarTimed), _i, _vp] + [_vp] * 4 + [_vp]),
+    "gsr_sugar_timed_backward": (_i, [_P(SugarTimed), _i, _vp] + [_vp] * 2 + [_vp] * 4 + [_vp] * 5 + [_vp, _sz, _vp]),
     "gsr_sugar_arap_workspace_bytes": (_sz, [_i, _i]),
-    "gsr_sugar_arap_forward": (_i, [_i] * 4 + [_vp] * 6 + [_vp] + [_vp, _sz, _vp]),
-    "gsr_sugar_arap_backward": (_i, [_i] * 4 + [_vp] * 6 + [_vp] + [_vp] * 2 + [_vp]),
+    "gsr_sugar_arap_forward": (_i, [_P(SugarArap)] + [_vp] + [_vp, _sz, _vp]),
+    "gsr_sugar_arap_backward": (_i, [_P(SugarArap)] + [_vp] + [_vp] * 2 + [_vp]),
     "gsr_sugar_spline_workspace_bytes": (_sz, [_i, _i, _i]),
-    "gsr_sugar_spline_forward": (_i, [_i] * 4 + [_f] * 4 + [_vp] * 4 + [_vp] * 3 + [_vp]),
-    "gsr_sugar_spline_backward": (_i, [_i] * 4 + [_f] * 4 + [_vp] * 4 + [_vp] * 3 + [_vp] * 3 + [_vp, _sz, _vp]),
+    "gsr_sugar_spline_forward": (_i, [_P(SugarSpline)] + [_vp] * 3 + [_vp]),
+    "gsr_sugar_spline_backward": (_i, [_P(SugarSpline)] + [_vp] * 3 + [_vp] * 3 + [_vp, _sz, _vp]),
     "gsr_set_geom_bytes": (_sz, [_i, _i]),
     "gsr_set_binning_bytes": (_sz, [_i, _i, ctypes.POINTER(_i), _i, _i]),
     "gsr_set_image_bytes": (_sz, [_i, _i, _ip, _i, _i, _i]),
@@ -176,7 +213,7 @@ def host_trace_read(reset: bool = True) -> dict:
     return out
 
 
-ABI_VERSION = 8  # include/gsr.h GSR_ABI_VERSION this binding is written against
+ABI_VERSION = 9  # include/gsr.h GSR_ABI_VERSION this binding is written against
 
 
 def load_library(path: str | None = None):

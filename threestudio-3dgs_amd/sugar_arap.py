@@ -109,10 +109,11 @@ class _ArapEnergy(torch.autograd.Function):
     """(vert_xyz, vert_rot) -> energy (T,)."""
 
     @staticmethod
-    def _args(vert_xyz, vert_rot, binding, form):
-        b = binding
-        return (int(vert_xyz.shape[0]), b.n_verts, b.n_edges, form, _gsr._ptr(b.verts), _gsr._ptr(b.offsets),
-                _gsr._ptr(b.nbr), _gsr._ptr(b.w), _gsr._ptr(vert_xyz), _gsr._ptr(vert_rot))
+    def _in(vert_xyz, vert_rot, binding, form):
+        """The gsr_sugar_arap of these tensors (addresses only: the caller keeps the tensors)."""
+        p, b = _gsr._ptr, binding
+        return _gsr.SugarArap(T=int(vert_xyz.shape[0]), V=b.n_verts, E=b.n_edges, rot_form=form, verts=p(b.verts),
+                              w=p(b.w), vert_xyz=p(vert_xyz), vert_rot=p(vert_rot), offsets=p(b.offsets), nbr=p(b.nbr))
 
     @staticmethod
     def forward(ctx, vert_xyz, vert_rot, binding, form):
@@ -126,7 +127,7 @@ class _ArapEnergy(torch.autograd.Function):
         if T > 0 and V > 0:
             nbytes = int(lib.gsr_sugar_arap_workspace_bytes(T, V))
             ws = workspace(nbytes, dev)
-            _gsr._check(lib.gsr_sugar_arap_forward(*_ArapEnergy._args(vert_xyz, vert_rot, binding, form),
+            _gsr._check(lib.gsr_sugar_arap_forward(_ArapEnergy._in(vert_xyz, vert_rot, binding, form),
                                                    _gsr._ptr(energy), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
         return energy
 
@@ -141,7 +142,7 @@ class _ArapEnergy(torch.autograd.Function):
         lib = _gsr.load_library()
         (g,) = ups((g_energy,), dev)
         dxyz, drot = torch.empty_like(vert_xyz), torch.empty_like(vert_rot)
-        _gsr._check(lib.gsr_sugar_arap_backward(*_ArapEnergy._args(vert_xyz, vert_rot, ctx.binding, ctx.form),
+        _gsr._check(lib.gsr_sugar_arap_backward(_ArapEnergy._in(vert_xyz, vert_rot, ctx.binding, ctx.form),
                                                 _gsr._ptr(g), _gsr._ptr(dxyz), _gsr._ptr(drot), _gsr._stream(dev)))
         return dxyz, drot, None, None
 

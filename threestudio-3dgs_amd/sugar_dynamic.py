@@ -93,6 +93,22 @@ class SkinBinding(Binding):
         return cls(nbr, dist / dist.sum(dim=-1, keepdim=True), P)
 
 
+def _skin_in(verts, node_trans, node_rots, node_scales, node_xyz, binding, method):
+    """The gsr_sugar_skin of these tensors (addresses only: the caller keeps the tensors)."""
+    p, b = _gsr._ptr, binding
+    return _gsr.SugarSkin(T=int(node_trans.shape[0]), V=b.n_verts, P=b.n_nodes, K=b.n_neighbors, method=method,
+                          verts=p(verts), node_xyz=p(node_xyz), node_trans=p(node_trans), node_rots=p(node_rots),
+                          node_scales=p(node_scales), nbr=p(b.nbr), w=p(b.w))
+
+
+def _timed_in(vert_xyz, vert_rot, rotation0, vert_scale, log_scales, binding, thickness):
+    """The gsr_sugar_timed of these tensors (addresses only: the caller keeps the tensors)."""
+    p, b = _gsr._ptr, binding
+    return _gsr.SugarTimed(T=int(vert_xyz.shape[0]), V=b.n_verts, F=b.n_faces, G=b.n_per_face, vert_xyz=p(vert_xyz),
+                           vert_rot=p(vert_rot), rotation0=p(rotation0), vert_scale=p(vert_scale),
+                           log_scales=p(log_scales), faces=p(b.faces), thickness=thickness)
+
+
 class _SkinVertices(torch.autograd.Function):
     """(verts, node_trans, node_rots, node_scales) -> (vert_xyz, vert_rot, vert_scale)."""
 
@@ -100,7 +116,7 @@ class _SkinVertices(torch.autograd.Function):
     def forward(ctx, verts, node_trans, node_rots, node_scales, node_xyz, binding, method):
         dev = verts.device
         lib = _gsr.load_library()
-        T, P, V, K = int(node_trans.shape[0]), binding.n_nodes, binding.n_verts, binding.n_neighbors
+        T, P, V = int(node_trans.shape[0]), binding.n_nodes, binding.n_verts
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(verts, node_trans, node_rots, node_scales, node_xyz)
         ctx.binding, ctx.method = binding, method
@@ -111,9 +127,8 @@ class _SkinVertices(torch.autograd.Function):
             nbytes = int(lib.gsr_sugar_skin_workspace_bytes(T, V, P))
             ws = workspace(nbytes, dev)
             _gsr._check(lib.gsr_sugar_skin_forward(
-                T, V, P, K, method, _gsr._ptr(verts), _gsr._ptr(node_xyz), _gsr._ptr(node_trans),
-                _gsr._ptr(node_rots), _gsr._ptr(node_scales), _gsr._ptr(binding.nbr), _gsr._ptr(binding.w),
-                _gsr._ptr(xyz), _gsr._ptr(rot), _gsr._ptr(scale), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
+                _skin_in(verts, node_trans, node_rots, node_scales, node_xyz, binding, method), _gsr._ptr(xyz),
+                _gsr._ptr(rot), _gsr._ptr(scale), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
         return xyz, rot, scale
 
     @staticmethod
@@ -122,7 +137,7 @@ class _SkinVertices(torch.autograd.Function):
         verts, node_trans, node_rots, node_scales, node_xyz = ctx.saved_tensors
         binding, method = ctx.binding, ctx.method
         dev = verts.device
-        T, P, V, K = int(node_trans.shape[0]), binding.n_nodes, binding.n_verts, binding.n_neighbors
+        T, P, V = int(node_trans.shape[0]), binding.n_nodes, binding.n_verts
         if node_scales is None:
             g_scale = None
         zeros = [torch.zeros_like(t) if t is not None else None for t in (verts, node_trans, node_rots, node_scales)]
@@ -134,10 +149,9 @@ class _SkinVertices(torch.autograd.Function):
         nbytes = int(lib.gsr_sugar_skin_workspace_bytes(T, V, P))
         ws = workspace(nbytes, dev)
         _gsr._check(lib.gsr_sugar_skin_backward(
-            T, V, P, K, method, _gsr._ptr(verts), _gsr._ptr(node_xyz), _gsr._ptr(node_trans), _gsr._ptr(node_rots),
-            _gsr._ptr(node_scales), _gsr._ptr(binding.nbr), _gsr._ptr(binding.w), _gsr._ptr(binding.item_order),
-            _gsr._ptr(binding.node_offsets), *(_gsr._ptr(g) for g in g_ups), *(_gsr._ptr(g) for g in grads),
-            _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
+            _skin_in(verts, node_trans, node_rots, node_scales, node_xyz, binding, method),
+            _gsr._ptr(binding.item_order), _gsr._ptr(binding.node_offsets), *(_gsr._ptr(g) for g in g_ups),
+            *(_gsr._ptr(g) for g in grads), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
         return (*grads, None, None, None)
 
 
@@ -186,7 +200,7 @@ class _TimedGaussians(torch.autograd.Function):
         dev = vert_xyz.device
         lib = _gsr.load_library()
         T = int(vert_xyz.shape[0])
-        V, F, G, N = binding.n_verts, binding.n_faces, binding.n_per_face, binding.n_gaussians
+        F, N = binding.n_faces, binding.n_gaussians
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(vert_xyz, vert_rot, rotation0, vert_scale, log_scales)
         ctx.binding, ctx.thickness = binding, thickness
@@ -196,9 +210,8 @@ class _TimedGaussians(torch.autograd.Function):
         scaling = None if vert_scale is None else torch.empty((T, N, 3), **fopt)
         if T > 0 and F > 0:
             _gsr._check(lib.gsr_sugar_timed_forward(
-                T, V, F, G, N, _gsr._ptr(vert_xyz), _gsr._ptr(vert_rot), _gsr._ptr(rotation0),
-                _gsr._ptr(binding.faces), ctypes.c_void_p(binding.bary.data_ptr()), _gsr._ptr(vert_scale),
-                _gsr._ptr(log_scales), thickness, _gsr._ptr(xyz), _gsr._ptr(rotation), _gsr._ptr(normals),
+                _timed_in(vert_xyz, vert_rot, rotation0, vert_scale, log_scales, binding, thickness), N,
+                ctypes.c_void_p(binding.bary.data_ptr()), _gsr._ptr(xyz), _gsr._ptr(rotation), _gsr._ptr(normals),
                 _gsr._ptr(scaling), _gsr._stream(dev)))
         return xyz, rotation, normals, scaling
 
@@ -209,7 +222,7 @@ class _TimedGaussians(torch.autograd.Function):
         binding = ctx.binding
         dev = vert_xyz.device
         T = int(vert_xyz.shape[0])
-        V, F, G, N = binding.n_verts, binding.n_faces, binding.n_per_face, binding.n_gaussians
+        F, N = binding.n_faces, binding.n_gaussians
         if vert_scale is None:
             g_scaling = None
         inputs = (vert_xyz, vert_rot, rotation0, vert_scale, log_scales)
@@ -221,8 +234,7 @@ class _TimedGaussians(torch.autograd.Function):
         nbytes = int(lib.gsr_sugar_timed_workspace_bytes(T, F))
         ws = workspace(nbytes, dev)
         _gsr._check(lib.gsr_sugar_timed_backward(
-            T, V, F, G, N, _gsr._ptr(vert_xyz), _gsr._ptr(vert_rot), _gsr._ptr(rotation0), _gsr._ptr(binding.faces),
-            ctypes.c_void_p(binding.bary.data_ptr()), _gsr._ptr(vert_scale), _gsr._ptr(log_scales), ctx.thickness,
+            _timed_in(*inputs, binding, ctx.thickness), N, ctypes.c_void_p(binding.bary.data_ptr()),
             _gsr._ptr(binding.corner_order), _gsr._ptr(binding.vert_offsets), *(_gsr._ptr(g) for g in g_ups),
             *(_gsr._ptr(g) for g in grads), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
         return (*grads, None, None)

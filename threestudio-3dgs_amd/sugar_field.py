@@ -41,6 +41,14 @@ __all__ = ["neighbor_density", "get_field_values", "neighbor_normal_loss", "smal
 FIELD_MAX_K = 32  # include/gsr.h GSR_KNN_MAX_K
 
 
+def _field_in(x, centers, inv_sr, strengths, min_scale, nbr, row, density_factor):
+    """The gsr_sugar_field of these tensors (addresses only: the caller keeps the tensors)."""
+    p = _gsr._ptr
+    return _gsr.SugarField(M=int(x.shape[0]), K=int(nbr.shape[1]), N=int(centers.shape[0]), R=int(nbr.shape[0]),
+                           x=p(x), nbr=p(nbr), row=p(row), centers=p(centers), inv_sr=p(inv_sr),
+                           strengths=p(strengths), min_scale=p(min_scale), density_factor=density_factor)
+
+
 class _NeighborDensity(torch.autograd.Function):
     """(x, centers, inv_sr, strengths, min_scale) -> (density, beta_avg, op | None); nbr / row are index tensors."""
 
@@ -48,7 +56,7 @@ class _NeighborDensity(torch.autograd.Function):
     def forward(ctx, x, centers, inv_sr, strengths, min_scale, nbr, row, density_factor, want_op):
         dev = x.device
         lib = _gsr.load_library()
-        M, K, N, R = int(x.shape[0]), int(nbr.shape[1]), int(centers.shape[0]), int(nbr.shape[0])
+        M, K, N = int(x.shape[0]), int(nbr.shape[1]), int(centers.shape[0])
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(x, centers, inv_sr, strengths, min_scale, nbr, row)
         ctx.density_factor = density_factor
@@ -60,9 +68,8 @@ class _NeighborDensity(torch.autograd.Function):
             nbytes = int(lib.gsr_sugar_field_workspace_bytes(0, K, N))
             ws = workspace(nbytes, dev)
             _gsr._check(lib.gsr_sugar_field_forward(
-                M, K, N, R, _gsr._ptr(x), _gsr._ptr(nbr), _gsr._ptr(row), _gsr._ptr(centers), _gsr._ptr(inv_sr),
-                _gsr._ptr(strengths), _gsr._ptr(min_scale), density_factor, _gsr._ptr(density), _gsr._ptr(beta_avg),
-                _gsr._ptr(op), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
+                _field_in(x, centers, inv_sr, strengths, min_scale, nbr, row, density_factor), _gsr._ptr(density),
+                _gsr._ptr(beta_avg), _gsr._ptr(op), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
         if op is None:
             return density, beta_avg, None
         return density, beta_avg, op
@@ -72,7 +79,7 @@ class _NeighborDensity(torch.autograd.Function):
     def backward(ctx, g_density, g_beta, g_op):
         x, centers, inv_sr, strengths, min_scale, nbr, row = ctx.saved_tensors
         dev = x.device
-        M, K, N, R = int(x.shape[0]), int(nbr.shape[1]), int(centers.shape[0]), int(nbr.shape[0])
+        M, K, N = int(x.shape[0]), int(nbr.shape[1]), int(centers.shape[0])
         if M == 0 or (g_density is None and g_beta is None and g_op is None):
             grads = tuple(torch.zeros_like(t) for t in (x, centers, inv_sr, strengths, min_scale))
             return grads + (None, None, None, None)
@@ -82,10 +89,9 @@ class _NeighborDensity(torch.autograd.Function):
         nbytes = int(lib.gsr_sugar_field_workspace_bytes(M, K, N))
         ws = workspace(nbytes, dev)
         _gsr._check(lib.gsr_sugar_field_backward(
-            M, K, N, R, _gsr._ptr(x), _gsr._ptr(nbr), _gsr._ptr(row), _gsr._ptr(centers), _gsr._ptr(inv_sr),
-            _gsr._ptr(strengths), _gsr._ptr(min_scale), ctx.density_factor, _gsr._ptr(g_density), _gsr._ptr(g_beta),
-            _gsr._ptr(g_op), _gsr._ptr(dx), _gsr._ptr(dc), _gsr._ptr(dA), _gsr._ptr(ds), _gsr._ptr(dms),
-            _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
+            _field_in(x, centers, inv_sr, strengths, min_scale, nbr, row, ctx.density_factor), _gsr._ptr(g_density),
+            _gsr._ptr(g_beta), _gsr._ptr(g_op), _gsr._ptr(dx), _gsr._ptr(dc), _gsr._ptr(dA), _gsr._ptr(ds),
+            _gsr._ptr(dms), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
         return dx, dc, dA, ds, dms, None, None, None, None
 
 
@@ -206,6 +212,14 @@ def get_field_values(x, *, points, inv_scaled_rotation, strengths, scaling, knn_
     return fields
 
 
+def _normal_in(x, centers, normals, min_scale, op, own, nbr, per_sample):
+    """The gsr_sugar_normal of these tensors (addresses only: the caller keeps the tensors)."""
+    p = _gsr._ptr
+    return _gsr.SugarNormal(M=int(x.shape[0]), K=int(nbr.shape[1]), N=int(centers.shape[0]), R=int(nbr.shape[0]),
+                            x=p(x), own=p(own), nbr=p(nbr), per_sample=int(per_sample), centers=p(centers),
+                            normals=p(normals), min_scale=p(min_scale), op=p(op))
+
+
 class _NeighborNormalLoss(torch.autograd.Function):
     """(x, centers, normals, min_scale, op) -> loss (M,); own / nbr are index tensors.  Only normals gets a gradient."""
 
@@ -213,7 +227,7 @@ class _NeighborNormalLoss(torch.autograd.Function):
     def forward(ctx, x, centers, normals, min_scale, op, own, nbr, per_sample):
         dev = x.device
         lib = _gsr.load_library()
-        M, K, N, R = int(x.shape[0]), int(nbr.shape[1]), int(centers.shape[0]), int(nbr.shape[0])
+        M, K, N = int(x.shape[0]), int(nbr.shape[1]), int(centers.shape[0])
         fopt = dict(dtype=torch.float32, device=dev)
         loss = torch.empty((M,), **fopt)
         rec = torch.empty((M, 4), **fopt) if ctx.needs_input_grad[2] else None  # (r, Wc): all the backward keeps
@@ -221,8 +235,7 @@ class _NeighborNormalLoss(torch.autograd.Function):
             nbytes = int(lib.gsr_sugar_normal_workspace_bytes(0, K, N))
             ws = workspace(nbytes, dev)
             _gsr._check(lib.gsr_sugar_normal_forward(
-                M, K, N, R, _gsr._ptr(x), _gsr._ptr(own), _gsr._ptr(nbr), int(per_sample), _gsr._ptr(centers),
-                _gsr._ptr(normals), _gsr._ptr(min_scale), _gsr._ptr(op), _gsr._ptr(loss), _gsr._ptr(rec),
+                _normal_in(x, centers, normals, min_scale, op, own, nbr, per_sample), _gsr._ptr(loss), _gsr._ptr(rec),
                 _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
         ctx.save_for_backward(x, centers, normals, min_scale, op, own, nbr, rec)
         ctx.per_sample = per_sample
@@ -233,7 +246,7 @@ class _NeighborNormalLoss(torch.autograd.Function):
     def backward(ctx, g_loss):
         x, centers, normals, min_scale, op, own, nbr, rec = ctx.saved_tensors
         dev = x.device
-        M, K, N, R = int(x.shape[0]), int(nbr.shape[1]), int(centers.shape[0]), int(nbr.shape[0])
+        M, K, N = int(x.shape[0]), int(nbr.shape[1]), int(centers.shape[0])
         if not ctx.needs_input_grad[2]:
             return (None,) * 8
         if M == 0 or N == 0:
@@ -244,9 +257,8 @@ class _NeighborNormalLoss(torch.autograd.Function):
         nbytes = int(lib.gsr_sugar_normal_workspace_bytes(M, K, N))
         ws = workspace(nbytes, dev)
         _gsr._check(lib.gsr_sugar_normal_backward(
-            M, K, N, R, _gsr._ptr(x), _gsr._ptr(own), _gsr._ptr(nbr), int(ctx.per_sample), _gsr._ptr(centers),
-            _gsr._ptr(normals), _gsr._ptr(min_scale), _gsr._ptr(op), _gsr._ptr(rec), _gsr._ptr(g_loss),
-            _gsr._ptr(dnormals), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
+            _normal_in(x, centers, normals, min_scale, op, own, nbr, ctx.per_sample), _gsr._ptr(rec),
+            _gsr._ptr(g_loss), _gsr._ptr(dnormals), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
         return (None, None, dnormals) + (None,) * 5
 
 

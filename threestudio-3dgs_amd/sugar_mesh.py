@@ -111,6 +111,13 @@ def _bary_ptr(binding):
     return ctypes.c_void_p(binding.bary.data_ptr())
 
 
+def _mesh_in(verts, cplx, log_scales, binding):
+    """The gsr_sugar_mesh of these tensors (addresses only: the caller keeps the tensors)."""
+    p = _gsr._ptr
+    return _gsr.SugarMesh(V=binding.n_verts, F=binding.n_faces, G=binding.n_per_face, verts=p(verts),
+                          faces=p(binding.faces), cplx=p(cplx), log_scales=p(log_scales))
+
+
 class _BoundGaussians(torch.autograd.Function):
     """(verts, complex_numbers, log_scales) -> (xyz, scaling, rotation, normals)."""
 
@@ -118,7 +125,7 @@ class _BoundGaussians(torch.autograd.Function):
     def forward(ctx, verts, cplx, log_scales, binding, thickness):
         dev = verts.device
         lib = _gsr.load_library()
-        V, F, G, N = binding.n_verts, binding.n_faces, binding.n_per_face, binding.n_gaussians
+        F, N = binding.n_faces, binding.n_gaussians
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(verts, cplx, log_scales)
         ctx.binding = binding
@@ -127,9 +134,8 @@ class _BoundGaussians(torch.autograd.Function):
         rotation = torch.empty((N, 4), **fopt)
         if F > 0:
             _gsr._check(lib.gsr_sugar_mesh_forward(
-                V, F, G, N, _gsr._ptr(verts), _gsr._ptr(binding.faces), _bary_ptr(binding), _gsr._ptr(cplx),
-                _gsr._ptr(log_scales), thickness, _gsr._ptr(xyz), _gsr._ptr(scaling), _gsr._ptr(rotation),
-                _gsr._ptr(normals), _gsr._stream(dev)))
+                _mesh_in(verts, cplx, log_scales, binding), N, _bary_ptr(binding), thickness, _gsr._ptr(xyz),
+                _gsr._ptr(scaling), _gsr._ptr(rotation), _gsr._ptr(normals), _gsr._stream(dev)))
         return xyz, scaling, rotation, normals
 
     @staticmethod
@@ -138,7 +144,7 @@ class _BoundGaussians(torch.autograd.Function):
         verts, cplx, log_scales = ctx.saved_tensors
         binding = ctx.binding
         dev = verts.device
-        V, F, G, N = binding.n_verts, binding.n_faces, binding.n_per_face, binding.n_gaussians
+        V, F, N = binding.n_verts, binding.n_faces, binding.n_gaussians
         if F == 0 or all(g is None for g in (g_xyz, g_scaling, g_rotation, g_normals)):
             return torch.zeros_like(verts), torch.zeros_like(cplx), torch.zeros_like(log_scales), None, None
         lib = _gsr.load_library()
@@ -147,10 +153,9 @@ class _BoundGaussians(torch.autograd.Function):
         nbytes = int(lib.gsr_sugar_mesh_workspace_bytes(F, V))
         ws = workspace(nbytes, dev)
         _gsr._check(lib.gsr_sugar_mesh_backward(
-            V, F, G, N, _gsr._ptr(verts), _gsr._ptr(binding.faces), _bary_ptr(binding), _gsr._ptr(cplx),
-            _gsr._ptr(log_scales), _gsr._ptr(binding.corner_order), _gsr._ptr(binding.vert_offsets),
-            *(_gsr._ptr(g) for g in grads), _gsr._ptr(dverts), _gsr._ptr(dcplx), _gsr._ptr(dls), _gsr._ptr(ws), nbytes,
-            _gsr._stream(dev)))
+            _mesh_in(verts, cplx, log_scales, binding), N, _bary_ptr(binding), _gsr._ptr(binding.corner_order),
+            _gsr._ptr(binding.vert_offsets), *(_gsr._ptr(g) for g in grads), _gsr._ptr(dverts), _gsr._ptr(dcplx),
+            _gsr._ptr(dls), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
         return dverts, dcplx, dls, None, None
 
 

@@ -91,9 +91,13 @@ class SplineGrid:
                 f"start_time={self.start_time!r}, n_knots={self.n_knots})")
 
 
-def _grid_args(grid):
-    return (grid.n_knots, grid.degree, float(grid.start_time), float(grid.sampling_interval), float(grid.clamp_lo),
-            float(grid.clamp_hi))
+def _spline_in(knots_xyz, knots_rot, knots_scale, timestamps, grid):
+    """The gsr_sugar_spline of these tensors (addresses only: the caller keeps the tensors)."""
+    p = _gsr._ptr
+    return _gsr.SugarSpline(T=int(timestamps.shape[0]), P=int(knots_xyz.shape[1]), n_knots=grid.n_knots,
+                            degree=grid.degree, start=float(grid.start_time), interval=float(grid.sampling_interval),
+                            lo=float(grid.clamp_lo), hi=float(grid.clamp_hi), timestamps=p(timestamps),
+                            knots_xyz=p(knots_xyz), knots_rot=p(knots_rot), knots_scale=p(knots_scale))
 
 
 class _SplineAttributes(torch.autograd.Function):
@@ -112,8 +116,8 @@ class _SplineAttributes(torch.autograd.Function):
         scale = None if knots_scale is None else torch.empty((T, P, 3), **fopt)
         if T > 0 and P > 0:
             _gsr._check(lib.gsr_sugar_spline_forward(
-                T, P, *_grid_args(grid), _gsr._ptr(timestamps), _gsr._ptr(knots_xyz), _gsr._ptr(knots_rot),
-                _gsr._ptr(knots_scale), _gsr._ptr(xyz), _gsr._ptr(rot), _gsr._ptr(scale), _gsr._stream(dev)))
+                _spline_in(knots_xyz, knots_rot, knots_scale, timestamps, grid), _gsr._ptr(xyz), _gsr._ptr(rot),
+                _gsr._ptr(scale), _gsr._stream(dev)))
         return xyz, rot, scale
 
     @staticmethod
@@ -134,9 +138,8 @@ class _SplineAttributes(torch.autograd.Function):
         nbytes = int(lib.gsr_sugar_spline_workspace_bytes(T, P, grid.degree))
         ws = workspace(nbytes, dev)
         _gsr._check(lib.gsr_sugar_spline_backward(
-            T, P, *_grid_args(grid), _gsr._ptr(timestamps), _gsr._ptr(knots_xyz), _gsr._ptr(knots_rot),
-            _gsr._ptr(knots_scale), *(_gsr._ptr(g) for g in g_ups), *(_gsr._ptr(g) for g in grads), _gsr._ptr(ws),
-            nbytes, _gsr._stream(dev)))
+            _spline_in(knots_xyz, knots_rot, knots_scale, timestamps, grid), *(_gsr._ptr(g) for g in g_ups),
+            *(_gsr._ptr(g) for g in grads), _gsr._ptr(ws), nbytes, _gsr._stream(dev)))
         return (*grads, None, None)
 
 
