@@ -84,6 +84,9 @@ const char* gsr_version(void);
  *   9  the gsr_sugar_*_forward / _backward calls take their stage's inputs as one struct (gsr_sugar_field, _normal,
  *      _mesh, _skin, _timed, _arap, _spline) followed by the tables, gradients, outputs and workspace, which stay
  *      positional; the *_workspace_bytes sizers are unchanged.
+ *      Added under 9 (additive: no existing call changes, binders find the new calls by symbol):
+ *      gsr_sugar_deform_workspace_bytes / gsr_sugar_deform_forward / gsr_sugar_deform_backward (dynamic SuGaR: the
+ *      HexPlane deformation network that produces the control knots).
  */
 #define GSR_ABI_VERSION 9
 int gsr_abi_version(void);
@@ -818,6 +821,75 @@ int gsr_sugar_spline_forward(const gsr_sugar_spline* in, float* xyz, float* rot,
 int gsr_sugar_spline_backward(const gsr_sugar_spline* in, const float* dL_dxyz, const float* dL_drot,
                               const float* dL_dscale, float* dL_dknots_xyz, float* dL_dknots_rot,
                               float* dL_dknots_scale, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * gsr_sugar_deform_*: the HexPlane deformation network of dynamic SuGaR evaluated at T ticks x P fixed points
+ * (DeformationNetwork.forward_dynamic_delta, geometry/deformation.py, as compute_control_knots calls it through
+ * _get_timed_dg_attributes_wo_spline and _get_timed_vertex_attributes_wo_spline, geometry/dynamic_sugar.py:442-480,
+ * 577-615, with their rot + (0, 0, 0, 1) and normalise epilogue).  T P < 2^31, 4 P < 2^31.  The inputs are the fields
+ * of gsr_sugar_deform below.
+ * Coordinates: sample (t, p) sees (n_p, 2 tick_t - 1), n_p = (x_p - aabb[0]) (2 / (aabb[1] - aabb[0])) - 1.  Along axis
+ * d of level l with R = reso[l][d] texels the coordinate c = clamp((n + 1) / 2 (R - 1), 0, R - 1) (grid_sample's
+ * align_corners = True, padding_mode = "border") lies in cell i = floor(c) at f = c - i.  The caller computes i and f
+ * in fp64 once per (points, ticks): cell / frac (L,3,P) for the spatial axes, tcell / tfrac (T,) for time (the time
+ * resolution is the same on every level).  A cell is clamped to [0, R - 1] here; the upper texel i + 1 of a cell at
+ * the upper edge is outside the plane: it has weight 0 and is never dereferenced.
+ * HexPlane: L (1..4) levels, each the 6 planes of itertools.combinations(range(4), 2) in that order; plane (a, b) of
+ * level l is (32, reso[l][b], reso[l][a]) fp32, coordinate a along the width: planes[6 l + q].  Its sample is the
+ * bilinear mix of its four texels per channel; the level's feature is the product of its six samples, the K = 32 L
+ * features are the levels' in order.
+ * MLP (mlp[0..13]: feature_out weight (64,K) and bias, then per head pos, rot, scale: the residual layer's weight
+ * (64,64) and bias, the final layer's weight (H,64) and bias, H = 3, 4, 3; the scale head's four are NULL iff d_scale
+ * is 0):  h = W0 feat + b0;  per head r = relu(h), y = r + W1 r + b1, o = W2 y + b2.
+ * Outputs, frame-major: xyz (T,P,3) = o_pos;  rot (T,P,4) = o_rot + (0,0,0,1), divided by its norm iff normalize_rot;
+ * scale (T,P,3) = o_scale (required iff d_scale): the knots_xyz, knots_rot, knots_scale of gsr_sugar_spline_*.
+ * Backward: the exact derivative to the 6 L planes and the MLP tensors given (none to the points, ticks or aabb).
+ * dL_dxyz, dL_drot, dL_dscale: any may be NULL (zero).  Tables (HexPlaneBinding builds them; rows in ascending entry
+ * order; an entry whose corner is outside its plane is absent):
+ *   sp_offsets / sp_order   per texel of the spatial planes (levels in order, planes (0,1), (0,2), (1,2), texels
+ *                           row-major) the entries 4 p + 2 cy + cx whose corner (cx along the width) is that texel;
+ *   col_offsets / col_order per level, spatial axis and column the entries 2 p + cx;
+ *   t_offsets / t_order     per time row the entries 2 t + ct.
+ *   n_sp, n_col, n_t are the lengths of the three order arrays; offsets are clamped to them, an entry out of range or
+ *   not of the row's texel contributes nothing and is never used as an index.
+ * Writes in full dL_dplanes[6 l + q] (device pointers in a host array, shaped like the planes; a texel that no sample
+ * touches gets exactly +0.0: the caller does not zero them) and dL_dmlp[0..13] (as mlp; the scale head's are ignored
+ * when d_scale is 0).  relu' at exactly 0 is 0.  The factor of a plane's sample is the upstream gradient of its level's
+ * channel times the product of the other five samples (multiplied, never divided out).
+ * Sum orders (no atomics; two calls give the same bits): a texel's row is split into its even and its odd entries, each
+ * added in ascending order from 0, then the two sums are added; a time-plane texel walks its column row outside and
+ * its time row inside.  Weights and biases: block b of B = min(256, ceil(P / 8)) owns the points 8 (b + B i) + w, wave
+ * w = 0..7, i = 0, 1, ...; per point the ticks ascend; the matrices of feature_out and of the residual layers are summed
+ * per block (round i, tick, wave in that order), the other tensors per wave, then the partial sums are added in block
+ * (and wave) order.  Precision: fp64 arithmetic from the fp32 inputs and the fp64 frac; every output and gradient is
+ * rounded to fp32 once (what passes between the backward's kernels is fp64).
+ * workspace (backward only): gsr_sugar_deform_workspace_bytes(T, P, L) bytes of device memory (256-B aligned):
+ * 256 L (T P + 2 P) bytes of fp64 rows and 8 B (20480 + 8192) bytes of partial sums.  The forward is one launch, the
+ * backward four, on `stream`; the library allocates nothing.  T = 0 or P = 0 launches nothing and writes nothing.
+ */
+#define GSR_DEFORM_MAX_L 4
+#define GSR_DEFORM_MLP 14
+#define GSR_DEFORM_OUT 10
+typedef struct gsr_sugar_deform {
+  int T, P, L;               /* ticks, points, levels */
+  int d_scale;               /* the scale head is evaluated */
+  int normalize_rot;         /* rot is divided by its norm (the graph-node variant) */
+  int n_sp, n_col, n_t;      /* lengths of sp_order, col_order, t_order (backward only) */
+  const int* reso;           /* HOST (L,4): texels of level l along x, y, z, time; each >= 2 */
+  const float* const* planes; /* HOST array of 6 L device pointers */
+  const float* const* mlp;   /* HOST array of 14 device pointers */
+  const int* cell;           /* (L,3,P) int32 */
+  const double* frac;        /* (L,3,P) fp64 in [0, 1) */
+  const int* tcell;          /* (T,) int32 */
+  const double* tfrac;       /* (T,) fp64 */
+} gsr_sugar_deform;
+size_t gsr_sugar_deform_workspace_bytes(int T, int P, int L);
+int gsr_sugar_deform_forward(const gsr_sugar_deform* in, float* xyz, float* rot, float* scale, void* stream);
+int gsr_sugar_deform_backward(const gsr_sugar_deform* in, const int* sp_order, const int* sp_offsets,
+                              const int* col_order, const int* col_offsets, const int* t_order, const int* t_offsets,
+                              const float* dL_dxyz, const float* dL_drot, const float* dL_dscale,
+                              float* const* dL_dplanes, float* const* dL_dmlp, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /*
  * The view-segmented stable LSD radix sort that every sort of this library runs (the depth sort, the tile sort and

@@ -838,6 +838,77 @@ int gsr_sugar_spline_backward(const gsr_sugar_spline* in, const float* dL_dxyz, 
   return last_launch();
 }
 
+// ---- the HexPlane deformation network (gsr_deform.hip) ----------------------------------------------
+static int deform_check(const gsr_sugar_deform& c) {
+  if (c.L < 1 || c.L > GSR_DEFORM_MAX_L) return fail(GSR_EINVAL, "%s", "L must be in 1..4");
+  if (c.T < 0 || c.P < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if (!below_2_31(c.T, c.P) || !below_2_31(4, c.P)) return fail(GSR_EINVAL, "%s", "T x P and 4 P must stay below 2^31");
+  if (c.reso == nullptr || c.planes == nullptr || c.mlp == nullptr) return null_argument();
+  long long texels = 0;
+  for (int l = 0; l < c.L; ++l) {
+    for (int d = 0; d < 4; ++d)
+      if (c.reso[4 * l + d] < 2) return fail(GSR_EINVAL, "%s", "every resolution must be at least 2");
+    if (c.reso[4 * l + 3] != c.reso[3]) return fail(GSR_EINVAL, "%s", "the time resolution is the same on every level");
+    for (int a = 0; a < 4; ++a)
+      for (int b = a + 1; b < 4; ++b) {
+        const long long n = (long long)c.reso[4 * l + a] * c.reso[4 * l + b];
+        if (n * 32 >= (1ll << 31)) return fail(GSR_EINVAL, "%s", "a plane must stay below 2^31 elements");
+        texels += n;
+      }
+  }
+  if (texels >= (1ll << 31)) return fail(GSR_EINVAL, "%s", "the planes must stay below 2^31 texels");
+  for (int i = 0; i < 6 * c.L; ++i)
+    if (c.planes[i] == nullptr) return fail(GSR_EINVAL, "%s", "null plane");
+  for (int i = 0; i < 10; ++i)
+    if (c.mlp[i] == nullptr) return null_argument();
+  for (int i = 10; i < GSR_DEFORM_MLP; ++i)
+    if ((c.mlp[i] != nullptr) != (c.d_scale != 0))
+      return fail(GSR_EINVAL, "%s", "the scale head is given iff d_scale is set");
+  if (c.T > 0 && c.P > 0 && (c.cell == nullptr || c.frac == nullptr || c.tcell == nullptr || c.tfrac == nullptr))
+    return null_argument();
+  if (((uintptr_t)c.frac | (uintptr_t)c.tfrac) & 7u) return fail(GSR_EINVAL, "%s", "frac and tfrac must be 8-byte aligned");
+  return GSR_OK;
+}
+
+size_t gsr_sugar_deform_workspace_bytes(int T, int P, int L) {
+  if (L < 1 || L > GSR_DEFORM_MAX_L) return 0;
+  return deform_workspace_bytes(T < 0 ? 0 : T, P < 0 ? 0 : P, L);
+}
+
+int gsr_sugar_deform_forward(const gsr_sugar_deform* in, float* xyz, float* rot, float* scale, void* stream) {
+  if (in == nullptr) return null_argument();
+  if (deform_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->T == 0 || in->P == 0) return nothing_to_do();
+  if (xyz == nullptr || rot == nullptr || (in->d_scale && scale == nullptr)) return null_argument();
+  launch_deform_forward(*in, xyz, rot, scale, (hipStream_t)stream);
+  return last_launch();
+}
+
+int gsr_sugar_deform_backward(const gsr_sugar_deform* in, const int* sp_order, const int* sp_offsets,
+                              const int* col_order, const int* col_offsets, const int* t_order, const int* t_offsets,
+                              const float* dL_dxyz, const float* dL_drot, const float* dL_dscale,
+                              float* const* dL_dplanes, float* const* dL_dmlp, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+  if (in == nullptr) return null_argument();
+  if (deform_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->T == 0 || in->P == 0) return nothing_to_do();
+  if (in->n_sp < 0 || in->n_col < 0 || in->n_t < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  if (sp_offsets == nullptr || col_offsets == nullptr || t_offsets == nullptr || dL_dplanes == nullptr ||
+      dL_dmlp == nullptr || workspace == nullptr || (in->n_sp > 0 && sp_order == nullptr) ||
+      (in->n_col > 0 && col_order == nullptr) || (in->n_t > 0 && t_order == nullptr))
+    return null_argument();
+  for (int i = 0; i < 6 * in->L; ++i)
+    if (dL_dplanes[i] == nullptr) return null_argument();
+  for (int i = 0; i < (in->d_scale ? GSR_DEFORM_MLP : 10); ++i)
+    if (dL_dmlp[i] == nullptr) return null_argument();
+  if (((uintptr_t)workspace & 7u) != 0) return fail(GSR_EINVAL, "%s", "workspace must be 8-byte aligned");
+  if (workspace_bytes < deform_workspace_bytes(in->T, in->P, in->L))
+    return fail(GSR_EINVAL, "%s", "workspace too small");
+  const DeformCsr t{sp_order, sp_offsets, col_order, col_offsets, t_order, t_offsets};
+  launch_deform_backward(*in, t, dL_dxyz, dL_drot, dL_dscale, dL_dplanes, dL_dmlp, workspace, (hipStream_t)stream);
+  return last_launch();
+}
+
 // ---- the view-segmented radix sort (tests: every sort of the library runs seg_sort) -----------------
 struct SortWork {
   uint32_t *keys2, *vals2, *counts, *totals;

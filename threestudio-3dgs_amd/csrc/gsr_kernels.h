@@ -321,6 +321,18 @@ void launch_spline_forward(const SplineCall& c, float* xyz, float* rot, float* s
 void launch_spline_backward(const SplineCall& c, const float* g_xyz, const float* g_rot, const float* g_scale,
                             float* dknots_xyz, float* dknots_rot, float* dknots_scale, void* workspace,
                             hipStream_t stream);
+// The HexPlane deformation network at T ticks x P points (include/gsr.h gsr_sugar_deform_*) — gsr_deform.hip.  L
+// levels of six planes, the 14 MLP tensors; reso, planes and mlp are host arrays.  The backward's workspace holds the
+// fp64 dL/dfeature rows (T P, 32 L), two (P, 32 L) per-point rows and the partial sums of the weight gradients.
+using DeformCall = gsr_sugar_deform;
+struct DeformCsr {
+  const int *sp_order, *sp_offsets, *col_order, *col_offsets, *t_order, *t_offsets;
+};
+size_t deform_workspace_bytes(int T, int P, int L);
+void launch_deform_forward(const DeformCall& c, float* xyz, float* rot, float* scale, hipStream_t stream);
+void launch_deform_backward(const DeformCall& c, const DeformCsr& t, const float* g_xyz, const float* g_rot,
+                            const float* g_scale, float* const* dplanes, float* const* dmlp, void* workspace,
+                            hipStream_t stream);
 void launch_gauss_backward(const GaussBackwardArgs& a, ViewGradArgs va, const AccumArgs& b, hipStream_t stream);
 
 }  // namespace gsr

@@ -96,10 +96,15 @@ class SugarSpline(ctypes.Structure):
                 + _fields(_vp, "timestamps knots_xyz knots_rot knots_scale"))
 
 
+class SugarDeform(ctypes.Structure):
+    _fields_ = (_fields(_i, "T P L d_scale normalize_rot n_sp n_col n_t") + [("reso", _ip)]
+                + _fields(_vpp, "planes mlp") + _fields(_vp, "cell frac tcell tfrac"))
+
+
 STRUCTS = {"gsr_set_scene": SetScene, "gsr_set_state": SetState, "gsr_set_outputs": SetOutputs,
            "gsr_set_grads": SetGrads, "gsr_sugar_field": SugarField, "gsr_sugar_normal": SugarNormal,
            "gsr_sugar_mesh": SugarMesh, "gsr_sugar_skin": SugarSkin, "gsr_sugar_timed": SugarTimed,
-           "gsr_sugar_arap": SugarArap, "gsr_sugar_spline": SugarSpline}
+           "gsr_sugar_arap": SugarArap, "gsr_sugar_spline": SugarSpline, "gsr_sugar_deform": SugarDeform}
 
 # name -> (restype, argtypes); must match include/gsr.h exactly (checked by tests/test_abi.py)
 SIGNATURES = {
@@ -161,6 +166,10 @@ SIGNATURES = {
     "gsr_sugar_spline_workspace_bytes": (_sz, [_i, _i, _i]),
     "gsr_sugar_spline_forward": (_i, [_P(SugarSpline)] + [_vp] * 3 + [_vp]),
     "gsr_sugar_spline_backward": (_i, [_P(SugarSpline)] + [_vp] * 3 + [_vp] * 3 + [_vp, _sz, _vp]),
+    "gsr_sugar_deform_workspace_bytes": (_sz, [_i, _i, _i]),
+    "gsr_sugar_deform_forward": (_i, [_P(SugarDeform)] + [_vp] * 3 + [_vp]),
+    # (the six tables, three upstream gradients, the host arrays of plane and MLP gradient pointers, workspace)
+    "gsr_sugar_deform_backward": (_i, [_P(SugarDeform)] + [_vp] * 6 + [_vp] * 3 + [_vpp] * 2 + [_vp, _sz, _vp]),
     "gsr_set_geom_bytes": (_sz, [_i, _i]),
     "gsr_set_binning_bytes": (_sz, [_i, _i, ctypes.POINTER(_i), _i, _i]),
     "gsr_set_image_bytes": (_sz, [_i, _i, _ip, _i, _i, _i]),
@@ -234,7 +243,10 @@ def load_library(path: str | None = None):
         raise ImportError(f"diff_gaussian_rasterization: {p} has C-ABI revision {got}, this binding needs "
                           f"{ABI_VERSION}; rebuild it with `make -C threestudio-3dgs_amd/csrc`")
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:  # (a call added under the same revision: a library built before it)
+            raise ImportError(f"diff_gaussian_rasterization: {p} does not export {name}; "
+                              "rebuild it with `make -C threestudio-3dgs_amd/csrc`")
         fn.restype = res
         fn.argtypes = args
     if path is None:
