@@ -39,7 +39,7 @@ def main():
     sc2 = dict(sc, colors_precomp=scene["normals"])
     if two:
         # the C5 test's upstream gradients: the torch fp32 epilogue on the oracle's fp32 outputs of both calls
-        import test_gpu_configs as tc
+        import gsr_testutil as tc
         import torch_reference as tr
         from diff_gaussian_rasterization.cameras import orbit_c2w, ray_bundle
 

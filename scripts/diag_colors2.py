@@ -3,8 +3,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in ("threestudio-3dgs_amd", "oracle", "tests"):
     sys.path.insert(0, os.path.join(ROOT, p))
 import numpy as np, torch
-from gsr_testutil import gs, make_camera
-from test_gpu_configs import _settings
+from gsr_testutil import _settings, gs, make_camera
 from diff_gaussian_rasterization.batched import rasterize_views
 scene = gs.make_scene(15_000, sh_degree=1, seed=44)
 rng = np.random.default_rng(4)

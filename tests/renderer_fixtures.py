@@ -21,11 +21,13 @@ swap it for the torch formulation (tests/torch_reference.render) together with t
 from __future__ import annotations
 
 import math
+import os
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
+import gsr_synthetic as gs
 import torch_reference as tr
 from diff_gaussian_rasterization import GaussianRasterizationSettings
 from diff_gaussian_rasterization.batch_renderer import GaussianBatchRenderer, material_params
@@ -303,3 +305,49 @@ def loss_of(out, seed=1):
             w = torch.randn(out[k].shape, generator=g, dtype=torch.float64).to(out[k].device, out[k].dtype)
             total = total + (out[k] * w).sum()
     return total
+
+
+# ---- one training step of the background renderer (tests/test_gpu_batch_renderer.py, tests/test_gpu_rccl.py) ---------
+H, W = 96, 128
+
+
+def _scene(mode):
+    if mode in ("sugar_normal", "sugar_shading"):
+        s = gs.make_sugar_scene(4, sh_degree=0, seed=2)
+        s["shs"] = s["shs"][:, :1]
+        return s
+    return gs.make_scene(20_000, sh_degree=3, seed=4)
+
+
+def _step(rank_world, B, tmp, tag, overlap=False):
+    """One training step of the background renderer on this process's views; saves the results.  overlap:
+    the rasterizer's per-Gaussian gradients are summed over ranks inside its backward (ChunkedGradReduce)
+    instead of by allreduce_grads afterwards."""
+    import torch.distributed as dist
+
+    import densify_reference as dr
+    from diff_gaussian_rasterization.view_shard import (ChunkedGradReduce, allreduce_grads, replica_checksum,
+                                                        update_states_sharded)
+
+    rank, world = rank_world
+    scene = _scene("background")
+    r = FakeRenderer("background", scene, "cuda")
+    model = dr.DensifyModel(scene, "cuda", densify_grad_threshold=2e-4)
+    r.geometry = model
+    if overlap:
+        r.grad_reduce = ChunkedGradReduce(n_chunks=3)
+    batch = make_batch(B, H, W, "cuda", seed=5)
+    out = r.batch_forward(batch)
+    loss_of(out).backward()
+    params = model.parameters()
+    if not overlap:
+        allreduce_grads(params)
+    else:
+        assert r.grad_reduce.launched == (1 if dist.is_initialized() else 0)
+    grads = [p.grad.detach().cpu().numpy().copy() for p in params]
+    update_states_sharded(model, 5, out)
+    same = replica_checksum(model.parameters() + [model.max_radii2D]) if world > 1 else True
+    np.savez(os.path.join(tmp, f"{tag}{rank}.npz"), comp_rgb=out["comp_rgb"].detach().cpu().numpy(),
+             P=model.get_xyz.shape[0], same=same, **{f"g{i}": g for i, g in enumerate(grads)})
+    if world > 1:
+        dist.barrier()

@@ -8,6 +8,7 @@ reference; float32: the "fp32 null" the GPU bars are calibrated on).  Written fr
 pypose's ``matrix()`` spelled out (``sugar_dynamic_reference.qmatrix``: no normalisation)."""
 import torch
 
+from sugar_cases import check_against_null
 from sugar_dynamic_reference import qmatrix
 
 
@@ -77,3 +78,24 @@ def evaluate(dtype, vert_xyz, vert_rot, verts, rings, w, up):
     gx, gr = torch.autograd.grad((e * up.to(dtype)).sum(), [x, r], allow_unused=True)
     return {"energy": e.detach(), "dvert_xyz": torch.zeros_like(x) if gx is None else gx,
             "dvert_rot": torch.zeros_like(r) if gr is None else gr}
+
+
+ARAP_MESHES = ("tetrahedron", "icosphere1", "fan40", "sliver")  # of tests/golden/reference_arap.npz
+ENERGY_FLOOR = 2.0 ** -23
+
+
+def check_arap(got, r64, r32, tag, grads=("dvert_xyz", "dvert_rot")):
+    """The bar of the ARAP tests: sugar_cases.check_against_null on the gradients; the (T,) energy has too few elements
+    for the null to be a stable sample, so per frame |got - ref64| / |ref64| <= max(2 x null, 2^-23), the second term
+    being one float32 rounding of an fp64 result, doubled.  Prints its figures."""
+    check_against_null(got, r64, r32, grads, tag)
+    e, e64, e32 = got["energy"].double(), r64["energy"], r32["energy"].double()
+    assert got["energy"].dtype == torch.float32 and e.shape == e64.shape, (tag, e.shape)
+    for t in range(len(e64)):
+        scale = abs(float(e64[t]))
+        if scale == 0:
+            assert float(e[t]) == 0, (tag, t)
+            continue
+        err, null = abs(float(e[t] - e64[t])) / scale, abs(float(e32[t] - e64[t])) / scale
+        print(f"{tag} energy[{t}]: gpu {err:.3g}  fp32 null {null:.3g}")
+        assert err <= max(2 * null, ENERGY_FLOOR), (tag, t, err, null)

@@ -1,8 +1,10 @@
-"""What more than one SuGaR test module uses: the meshes, quaternions and error measure of the geometry stages and the
-scene, restatement and checker of the neighbour density field (tests/test_gpu_sugar_field.py describes its bar).  No
-tests here: the test modules import from this one and not from each other."""
+"""What more than one SuGaR test module uses: the meshes, quaternions, error measure, bar (``check_against_null``) and
+case skeleton (``NullCase``, ``backprop``) of the geometry stages, and the scene, restatements and checker of the
+neighbour density field and normal loss (tests/test_gpu_sugar_field.py and tests/test_gpu_sugar_normal.py describe
+their bars).  No tests here: the test modules import from this one and not from each other."""
 import functools
 import math
+import os
 
 import numpy as np
 import pytest
@@ -17,6 +19,84 @@ D = torch.float64
 def _rel(a, b):
     scale = float(b.double().abs().max()) if b.numel() else 0.0
     return float((a.double() - b.double()).abs().max()) / scale if scale > 0 else 0.0
+
+
+def check_against_null(got, ref64, null32, keys, tag, *, null_ref=None, note=""):
+    """The bar of the geometry stages, stated once (tests/test_null_bar.py holds it to its word).  Per tensor:
+    float32, the reference's shape, and max |got - ref64| / max |ref64| <= 2 x the same figure of the fp32 null (which
+    is measured against null_ref where that is not ref64); where the reference is all zero, exactly zero.  Prints both
+    figures."""
+    null_ref = ref64 if null_ref is None else null_ref
+    for k in keys:
+        assert got[k].dtype == torch.float32 and got[k].shape == ref64[k].shape, (tag, k, got[k].shape)
+        err, bar = _rel(got[k], ref64[k]), 2 * _rel(null32[k], null_ref[k])
+        print(f"{tag} {k}: gpu {err:.3g}  fp32 null {bar / 2:.3g}{note}")
+        if not ref64[k].any():
+            assert not got[k].any(), (tag, k)  # nothing contributes: exactly zero
+        else:
+            assert torch.isfinite(got[k]).all() and err <= bar, (tag, k, err, bar)
+
+
+# ---- the fixtures computed by the reference's own code (tests/golden/reference_*.npz, made by make_golden*.py) -------
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
+OUT_BAR, GRAD_BAR = 1e-12, 1e-10
+
+
+@functools.lru_cache(maxsize=None)
+def fixture(name):
+    with np.load(os.path.join(GOLDEN, f"reference_{name}.npz")) as z:
+        return {k: torch.from_numpy(z[k]) for k in z.files}
+
+
+def close(got, want, bar, tag):
+    assert got.dtype == want.dtype == D and got.shape == want.shape, (tag, got.dtype, got.shape, want.shape)
+    err = _rel(got, want)
+    print(f"{tag}: {err:.3g} (bar {bar:g})")
+    if not want.any():
+        assert not got.any(), tag
+    else:
+        assert err <= bar, (tag, err, bar)
+
+
+def null_is_usable(z, prefix, keys):
+    """Every float32 tensor is finite, and differs from the float64 one (so 2 x the null is a bar, not zero), unless
+    the float64 tensor is all zero (then the GPU must give exact zeros)."""
+    for k in keys:
+        a, b = z[f"{prefix}{k}_f32"], z[f"{prefix}{k}_f64"]
+        assert a.dtype == torch.float32 and b.dtype == D and a.shape == b.shape, (prefix, k)
+        assert torch.isfinite(a).all() and torch.isfinite(b).all(), (prefix, k)
+        assert _rel(a, b) > 0 or not b.any(), (prefix, k)
+
+
+def backprop(out, out_names, leaves, grad_names, ups, which):
+    """`got` of a stage called on the GPU: its outputs by name and, under grad_names, the gradients of
+    sum((o * up).sum()) over the outputs named in `which`.  Outputs and leaves that are None are left out."""
+    loss = sum((o * ups[k].cuda()).sum() for k, o in zip(out_names, out) if k in which)
+    have = [(k, t) for k, t in zip(grad_names, leaves) if t is not None]
+    grads = torch.autograd.grad(loss, [t for _, t in have])
+    got = {k: o.detach().cpu() for k, o in zip(out_names, out) if o is not None}
+    got.update({k: g.cpu() for (k, _), g in zip(have, grads)})
+    return got
+
+
+class NullCase:
+    """What the cases of the geometry stages share.  A case draws its inputs, `ups` (the upstream gradients by output
+    name) and `keys` (what is compared), and has evaluate(dtype, ups), its reference, and gpu(which), its stage."""
+
+    outputs = property(lambda self: tuple(self.ups))
+
+    def references(self, ups):
+        return tuple(self.evaluate(dt, ups) for dt in (torch.float64, torch.float32))
+
+    def reference(self, which):
+        """The fp64 reference and the fp32 null for the upstream gradients named in `which`, computed once."""
+        refs = self.__dict__.setdefault("_refs", {})
+        if which not in refs:
+            refs[which] = self.references({k: self.ups[k] for k in which})
+        return refs[which]
+
+    def check(self, got, which=None, tag=""):
+        check_against_null(got, *self.reference(self.outputs if which is None else tuple(which)), self.keys, tag)
 
 
 def _fan(n=200):
@@ -235,3 +315,63 @@ def _inputs(M=M_FULL, K=16):
 def _full_case(K):
     inp, gi, idx, ups = _inputs(M_FULL, K)
     return _Case(inp, idx, _mask(idx, inp["centers"].shape[0]), 1.0, ups)
+
+
+def _compose64(density, op, beta_avg, ms_nb, mode, log_beta, threshold, clampv):
+    """The reference's remainder (utils/sugar_utils.py:313-341, 417-471) in fp64 from fp64 density / op / beta_avg."""
+    dens = density.clone()
+    m = dens >= 1.
+    dens[m] = dens[m] / (dens[m] + 1e-12)
+    if mode == "learnable":
+        beta = torch.exp(log_beta.double()).expand(len(density))
+    elif mode == "average":
+        beta = beta_avg
+    else:
+        osum = op.sum(-1, keepdim=True)
+        beta = (ms_nb * (op / osum.clamp(min=clampv))).sum(-1)
+        beta[osum[..., 0] == 0.] = ms_nb.max()
+    t = torch.sqrt(-2. * torch.log(dens.clamp(min=clampv)))
+    return dens, beta, t, beta * (t - math.sqrt(-2. * math.log(min(threshold, 1.))))
+
+
+FIELD_RUNS = {"a": ("average", 1.0, True, True), "w": ("weighted_average", 1.3, True, True),
+              "l": ("learnable", 1.0, False, False)}  # beta_mode, density_factor, return_sdf, opacities returned
+FIELD_LEAVES = ("x", "points", "inv_sr", "strengths", "scaling", "log_beta")
+
+
+def field_keys(run, grads=True):
+    mode, df, sdf_on, want_op = FIELD_RUNS[run]
+    keys = ("density", "beta") + (("sdf",) if sdf_on else ()) + (("closest_gaussian_opacities",) if want_op else ())
+    return keys + (tuple("d" + k for k in FIELD_LEAVES) if grads and run != "a" else ())
+
+
+# ---- the neighbour-normal loss ---------------------------------------------------------------------------------------
+WMIN = 1e-6
+
+
+def _normal(dtype, inp, idx, own, ok, own_ok, g, literal=False):
+    """loss (M,), dL/dnormals (N, 3), and the intermediates, of the reference's composition in `dtype`.  `literal`:
+    r summed as the reference writes it, n_i - sum_k wh s n_j (the fp32 null); otherwise in the equal arrangement
+    (1 - W / Wc) n_i + sum_k wh (n_i - s n_j), which does not cancel n_i against the sample's own slot (the fp64
+    checker: see the docstring of tests/test_gpu_sugar_normal.py)."""
+    x, c, ms, op = (inp[k].to(dtype) for k in ("x", "centers", "min_scale", "op"))
+    nrm = inp["normals"].to(dtype).clone().requires_grad_()
+    n = c.shape[0]
+    j = idx.clamp(0, max(n - 1, 0))
+    ni = nrm[own.clamp(0, max(n - 1, 0))]
+    nj = nrm[j]
+    dot = (nj * ni[:, None]).sum(dim=-1, keepdim=True)
+    njs = nj * torch.sign(dot).detach()
+    a = ((x[:, None] - c[j]) * njs).sum(dim=-1).abs().detach()
+    w = op * a / ms[j].clamp(min=1e-6) ** 2 * ok
+    W = w.sum(dim=-1).detach()
+    wh = w / W.unsqueeze(-1).clamp(min=WMIN)
+    if literal:
+        r = ni - (wh[..., None] * njs).sum(dim=-2)
+    else:
+        rest = torch.where(W >= WMIN, torch.zeros_like(W), 1 - W / W.clamp(min=WMIN))
+        r = rest[:, None] * ni + (wh[..., None] * (ni[:, None] - njs)).sum(dim=-2)
+    loss = r.pow(2).sum(dim=-1) * own_ok
+    grad, = torch.autograd.grad((loss * g.to(dtype)).sum(), nrm) if len(loss) else (torch.zeros_like(nrm),)
+    return dict(loss=loss.detach(), dnormals=grad, r=r.detach(), wh=wh.detach(), s=torch.sign(dot).detach()[..., 0],
+                dot=dot.detach()[..., 0], W=W, nj=nj.detach(), ni=ni.detach(), j=j)

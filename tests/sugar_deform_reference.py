@@ -4,7 +4,9 @@ geometry/deformation.py at T ticks x P points with the epilogue of ``_get_timed_
 gather is written out (no ``grid_sample``), so that this is an independent statement; tests/test_sugar_deform.py pins it
 to the reference's own code through tests/golden/reference_deform.npz."""
 import itertools
+import os
 
+import numpy as np
 import torch
 
 COMBOS = tuple(itertools.combinations(range(4), 2))
@@ -81,3 +83,41 @@ def evaluate(dtype, points, ticks, aabb, planes, mlp, ups, normalize_rot=True):
 def keys(n_planes, n_mlp):
     return (("xyz", "rot") + (("scale",) if n_mlp == 14 else ()) + tuple(f"dplane{i}" for i in range(n_planes))
             + tuple(f"dmlp{i}" for i in range(n_mlp)))
+
+
+# ---- the reference's own DeformationNetwork: tests/golden/reference_deform.npz ---------------------------------------
+HERE = os.path.dirname(os.path.abspath(__file__))
+CASES = {"dg": (True, True), "dg_noscale": (True, False), "vert": (False, True)}  # normalize_rot, d_scale
+_CACHE = {}
+
+
+def fixture():
+    if "z" not in _CACHE:
+        z = np.load(os.path.join(HERE, "golden", "reference_deform.npz"))
+        _CACHE["z"] = {k: (z[k] if z[k].dtype.kind == "U" else torch.from_numpy(z[k])) for k in z.files}
+    return _CACHE["z"]
+
+
+def fixture_weights(z, d_scale):
+    from sugar_deform import DeformationWeights
+
+    return DeformationWeights.from_state_dict({k: z["w_" + k] for k in z["names"]}, d_scale)
+
+
+def fixture_reference(z, case, tag, weights):
+    """{key of sugar_deform_reference.evaluate: the reference's tensor} for what the fixture stores of the case."""
+    out = {k: z[f"{case}_{n}_{tag}"] for k, n in zip(OUTPUTS, ("xyz", "rotation", "scale"))
+           if f"{case}_{n}_{tag}" in z}
+    L6 = len(weights.planes)
+    for i, name in enumerate(weights.names):
+        key = f"{case}_d_{name}_{tag}"
+        if key in z:
+            out[f"dplane{i}" if i < L6 else f"dmlp{i - L6}"] = z[key]
+    return out
+
+
+def fixture_ups(z, d_scale):
+    ups = {"xyz": z["up_xyz"], "rot": z["up_rotation"]}
+    if d_scale:
+        ups["scale"] = z["up_scale"]
+    return ups

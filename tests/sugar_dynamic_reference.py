@@ -158,3 +158,15 @@ def evaluate_timed(dtype, inputs, faces, bary, thickness, ups):
     return _evaluate(lambda x: timed_gaussians_reference(x["vert_xyz"], x["vert_rot"], x["rotation0"], faces.long(),
                                                          bary, x["vert_scale"], x["log_scales"], thickness),
                      TIMED_INPUTS, TIMED_OUTPUTS, dtype, inputs, ups)
+
+
+# ---- the reference's own skinning and timed Gaussians: tests/golden/reference_dynamic.npz ----------------------------
+SKIN_KEYS = ("xyz", "rotation", "scale", "dverts", "dnode_trans", "dnode_rots", "dnode_scales")
+TIMED_KEYS = ("xyz", "rotation", "scale", "dvert_xyz", "dvert_rot", "drotation0", "dvert_scale", "dlog_scales")
+
+
+def tangent(g, q):
+    """The part of a gradient g to unit quaternions q that is orthogonal to q: its component along q is the derivative
+    with respect to the quaternion's norm."""
+    q = q.to(g.dtype)
+    return g - (g * q).sum(-1, keepdim=True) * q

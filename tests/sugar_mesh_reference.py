@@ -100,3 +100,11 @@ def row_sign(got_rotation, ref_rotation):
     """+-1 per row: the sign of the dot product of a quaternion row with the reference's (+1 at 0)."""
     d = (got_rotation.double() * ref_rotation.double()).sum(-1)
     return torch.where(d < 0, -torch.ones_like(d), torch.ones_like(d))
+
+
+# ---- the reference's own mesh-bound Gaussians: tests/golden/reference_mesh.npz ---------------------------------------
+MESH_KEYS = OUTPUTS + GRADS
+
+
+def mesh_fixture(z, G, tag):
+    return {k: z[f"G{G}_{'d' if k in GRADS else ''}{k}_{tag}"] for k in MESH_KEYS}

@@ -62,3 +62,14 @@ def evaluate(dtype, inputs, grid, timestamps, ups):
     a dict over SPLINE_INPUTS (knots_scale may be None); ups: the upstream gradients by output name (absent = zero)."""
     return _evaluate(lambda x: spline_reference(timestamps, x["knots_xyz"], x["knots_rot"], grid, x["knots_scale"]),
                      SPLINE_INPUTS, SPLINE_OUTPUTS, dtype, inputs, ups)
+
+
+# ---- the reference's own Spline: tests/golden/reference_spline.npz, read by sugar_cases.fixture("spline") ----------
+SPLINE_KEYS = ("xyz", "rotation", "scale", "dknots_xyz", "dknots_rot", "dknots_scale")
+
+
+def fixture_grid(z, degree):
+    from sugar_spline import SplineGrid
+
+    g = z[f"deg{degree}_grid"]
+    return SplineGrid(degree, g[1].item(), g[0].item(), int(z["knots_xyz"].shape[0]))

@@ -22,19 +22,9 @@ import torch
 
 import renderer_fixtures as rf
 from gsr_testutil import gs
+from renderer_fixtures import H, W, _scene, _step
 
 pytestmark = pytest.mark.gpu
-
-H, W = 96, 128
-
-
-def _scene(mode):
-    if mode in ("sugar_normal", "sugar_shading"):
-        s = gs.make_sugar_scene(4, sh_degree=0, seed=2)
-        s["shs"] = s["shs"][:, :1]
-        return s
-    return gs.make_scene(20_000, sh_degree=3, seed=4)
-
 
 def _close(a, b, tol, what):
     a = a.detach().double().cpu()
@@ -95,40 +85,6 @@ def _free_port():
     p = s.getsockname()[1]
     s.close()
     return p
-
-
-def _step(rank_world, B, tmp, tag, overlap=False):
-    """One training step of the background renderer on this process's views; saves the results.  overlap:
-    the rasterizer's per-Gaussian gradients are summed over ranks inside its backward (ChunkedGradReduce)
-    instead of by allreduce_grads afterwards."""
-    import torch.distributed as dist
-
-    import densify_reference as dr
-    from diff_gaussian_rasterization.view_shard import (ChunkedGradReduce, allreduce_grads, replica_checksum,
-                                                        update_states_sharded)
-
-    rank, world = rank_world
-    scene = _scene("background")
-    r = rf.FakeRenderer("background", scene, "cuda")
-    model = dr.DensifyModel(scene, "cuda", densify_grad_threshold=2e-4)
-    r.geometry = model
-    if overlap:
-        r.grad_reduce = ChunkedGradReduce(n_chunks=3)
-    batch = rf.make_batch(B, H, W, "cuda", seed=5)
-    out = r.batch_forward(batch)
-    rf.loss_of(out).backward()
-    params = model.parameters()
-    if not overlap:
-        allreduce_grads(params)
-    else:
-        assert r.grad_reduce.launched == (1 if dist.is_initialized() else 0)
-    grads = [p.grad.detach().cpu().numpy().copy() for p in params]
-    update_states_sharded(model, 5, out)
-    same = replica_checksum(model.parameters() + [model.max_radii2D]) if world > 1 else True
-    np.savez(os.path.join(tmp, f"{tag}{rank}.npz"), comp_rgb=out["comp_rgb"].detach().cpu().numpy(),
-             P=model.get_xyz.shape[0], same=same, **{f"g{i}": g for i, g in enumerate(grads)})
-    if world > 1:
-        dist.barrier()
 
 
 def _worker(rank, world, port, tmp, B, overlap=False):
@@ -468,8 +424,8 @@ def _c4_oracle_sums(single, B, S):
 
 def _c4_oracle_views(single, B, S, views):
     import oracle
-    from gsr_testutil import adjudicate, check_radii, flip_excuse, oracle_cam, run_oracle
-    from test_gpu_configs import _composite, _composite_upstream
+    from gsr_testutil import (_composite, _composite_upstream, adjudicate, check_radii, flip_excuse, oracle_cam,
+                              run_oracle)
 
     scene = gs.make_scene(C4_P, sh_degree=3, seed=0)
     w2c, proj, campos, bg_img = single["w2c"], single["proj"], single["campos"], single["bg_img"]

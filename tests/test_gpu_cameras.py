@@ -75,7 +75,7 @@ def test_mixed_view_set_vs_oracle(nviews):
     """One scene seen from near49, inside, the orbit and tele20 in one rasterize_views set.  The set's depth-key
     range and 3-pass flag live in one GeomState: the inside view alone needs the fourth sort pass, the others
     alone would not.  Images per view, means2D gradients per view, parameter gradients summed over the views."""
-    from test_gpu_configs import GRAD_KEYS, _gpu_views, _sum_grads, _view
+    from gsr_testutil import GRAD_KEYS, _gpu_views, _sum_grads, _view
 
     W, H = 128, 112
     scene = gs.make_scene(2000, sh_degree=1, seed=111)

@@ -21,91 +21,17 @@ import numpy as np
 import pytest
 
 import oracle
-from gsr_testutil import (adjudicate, check_forward, check_grads, check_radii, flip_excuse, gs, make_camera, oracle_cam,
-                          print_report, run_oracle)
+from gsr_testutil import (GRAD_KEYS, SUGAR_OUT, _composite, _composite_upstream, _gpu_views, _settings,
+                          _sugar_epilogue, _sum_grads, _view, adjudicate, check_forward, check_grads, check_radii, flip_excuse, gs, make_camera,
+                          oracle_cam, print_report, run_oracle)
 
 pytestmark = pytest.mark.gpu
-
-GRAD_KEYS = ["means3D", "opacity", "sh", "scales", "rotations"]
-TORCH_NAMES = dict(means3D="means3D", scales="scales", rotations="rotations", opacities="opacity", shs="sh",
-                   colors_precomp="colors")
 
 
 @pytest.fixture(autouse=True)
 def _parity_report():
     yield
     print_report()
-
-
-def _settings(cam, bg, deg, mod=1.0):
-    import torch
-
-    from diff_gaussian_rasterization import GaussianRasterizationSettings
-
-    dev = "cuda"
-    return GaussianRasterizationSettings(cam["H"], cam["W"], cam["tanx"], cam["tany"],
-                                         torch.tensor(bg, device=dev, dtype=torch.float32), mod,
-                                         torch.tensor(cam["view"], device=dev), torch.tensor(cam["proj"], device=dev),
-                                         deg, torch.tensor(cam["campos"], device=dev), False, False)
-
-
-def _gpu_views(scene, cams, bgs, ups=None, background=None):
-    """rasterize_views over `cams`; returns per-view numpy outputs, K, means2D grads and summed grads."""
-    import torch
-
-    from diff_gaussian_rasterization import _C
-    from diff_gaussian_rasterization.batched import rasterize_views
-
-    dev = "cuda"
-    keys = [k for k in ("means3D", "scales", "rotations", "opacities", "shs", "colors_precomp") if scene.get(k) is not None]
-    t = {k: torch.tensor(scene[k], device=dev, requires_grad=True) for k in keys}
-    P = scene["means3D"].shape[0]
-    V = len(cams)
-    m2s = [torch.zeros((P, 3), device=dev, requires_grad=True) for _ in cams]
-    bg_t = None if background is None else torch.tensor(background, device=dev, requires_grad=True)
-    settings = [_settings(c, b, int(scene.get("sh_degree", 0))) for c, b in zip(cams, bgs)]
-    c, r, d, a = rasterize_views(settings, t["means3D"], m2s, t["opacities"], shs=t.get("shs"),
-                                 colors_precomp=t.get("colors_precomp"), scales=t["scales"],
-                                 rotations=t["rotations"], background=bg_t)
-    Ks = [k for k, _, _ in list(_C.RECENT_FORWARDS)[-V:]]
-    out = dict(color=c.detach().cpu().numpy(), depth=d.detach().cpu().numpy(), alpha=a.detach().cpu().numpy(),
-               radii=r.cpu().numpy(), K=Ks)
-    if ups is not None:
-        gc = torch.stack([torch.tensor(u[0], device=dev) for u in ups])
-        gd = torch.stack([torch.tensor(u[1], device=dev) for u in ups])
-        ga = torch.stack([torch.tensor(u[2], device=dev) for u in ups])
-        ((c * gc).sum() + (d * gd).sum() + (a * ga).sum()).backward()
-        for k, v in t.items():
-            out["g_" + TORCH_NAMES[k]] = v.grad.cpu().numpy()
-        out["g_means2D"] = [m.grad.cpu().numpy() for m in m2s]
-        if bg_t is not None:
-            out["g_background"] = bg_t.grad.cpu().numpy()
-    return out
-
-
-def _view(out, v):
-    return dict(color=out["color"][v], depth=out["depth"][v], alpha=out["alpha"][v], radii=out["radii"][v])
-
-
-def _sum_grads(refs, prec, keys):
-    return {k: sum(np.asarray(r[prec][k], np.float64) for r in refs) for k in keys}
-
-
-def _composite(color, alpha, bg_hwc):
-    """renderer/diff_gaussian_rasterizer_background.py:129-132,139 in the arrays' precision, torch's op
-    order: color + (1 - alpha) * bg, then clamp(0, 1).  Returns (render, pre-clamp value)."""
-    one = color.dtype.type(1)
-    pre = color + (one - alpha) * bg_hwc.transpose(2, 0, 1).astype(color.dtype)
-    return np.clip(pre, 0, 1), pre
-
-
-def _composite_upstream(g_render, g_alpha, pre, bg_hwc):
-    """Gradients of the composite + clamp: dL/dcolor = g [0 <= pre <= 1], dL/dalpha += -sum_ch dL/dcolor bg,
-    dL/dbg = dL/dcolor (1 - alpha) (torch's clamp passes the gradient on the closed interval)."""
-    m = (pre >= 0) & (pre <= 1)
-    gcol = np.where(m, g_render.astype(pre.dtype), 0)
-    ga = g_alpha.astype(pre.dtype) - (gcol * bg_hwc.transpose(2, 0, 1).astype(pre.dtype)).sum(0, keepdims=True)
-    return gcol, ga
 
 
 # ------------------------------------------------------------------------------------------------
@@ -384,24 +310,6 @@ def test_split_backward_parity():
 
 # ------------------------------------------------------------------------------------------------
 # C5: the SuGaR normal renderer
-
-def _sugar_epilogue(torch, color, depth, alpha, normal, rays_o, rays_d, depth_normal):
-    """renderer/diff_sugar_rasterizer_normal.py:169-213 after the two rasterizer calls, one view (C,H,W).
-    depth_normal(depth, alpha) -> (normal_from_dist, normal_map_from_dist) (both gradient masked)."""
-    F = torch.nn.functional
-    nfd, nmap_dist = depth_normal(depth, alpha)
-    n = F.normalize(normal, dim=0)
-    n = torch.cat([-n[:2], n[2:]], 0)
-    nmap = n * 0.5 * alpha + 0.5
-    mask = alpha > 0.99
-    nmap = torch.where(mask.expand_as(nmap), nmap, nmap.detach())
-    depth_m = torch.where(mask, depth, depth.detach())
-    return dict(render=color.clamp(0, 1), normal=nmap, normal_from_dist=nmap_dist, mask=alpha, depth=depth_m,
-                raw_normal_from_dist=nfd)
-
-
-SUGAR_OUT = ("render", "normal", "normal_from_dist", "mask", "depth")
-
 
 @pytest.mark.slow
 def test_c5_sugar_normal_renderer():

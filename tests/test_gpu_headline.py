@@ -48,7 +48,7 @@ def test_headline_kernel_selection_vs_oracle():
     headline's tile-wave forward and the mask-culled lockstep backward.  Every view vs the oracle (composite,
     radii, K, means2D gradient row-wise), the parameter gradients summed over the 16 views vs the oracle's sums."""
     from diff_gaussian_rasterization import _C
-    from test_gpu_configs import GRAD_KEYS, _gpu_views, _view
+    from gsr_testutil import GRAD_KEYS, _gpu_views, _view
 
     spec = ("ball", 250_000, 3, 0)
     scene = oracle_pool.scene_of(spec)
@@ -83,7 +83,7 @@ def test_c5_kernel_selection_vs_oracle():
 
     from diff_gaussian_rasterization import _C
     from diff_gaussian_rasterization.batched import rasterize_views
-    from test_gpu_configs import _settings
+    from gsr_testutil import _settings
 
     spec1, spec2 = ("sugar", 4, 0, 5, True), ("sugar", 4, 0, 5, False)
     s1 = oracle_pool.scene_of(spec1)

@@ -266,7 +266,7 @@ def bitwise_case(kind, monkeypatch=None, fwd_kernel=None, between=None):
     import torch
 
     from diff_gaussian_rasterization.batched import rasterize_views
-    from test_gpu_configs import _settings
+    from gsr_testutil import _settings
 
     if fwd_kernel is not None:
         monkeypatch.setenv("GSR_FWD_KERNEL", fwd_kernel)

@@ -32,7 +32,7 @@ s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.clos
 os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
 dist.init_process_group("nccl", device_id=torch.device("cuda", 0))  # before any other GPU work here
 assert dist.get_backend() == "nccl" and dist.get_world_size() == 1
-import test_gpu_batch_renderer as t
+import renderer_fixtures as t
 from diff_gaussian_rasterization import view_shard
 view_shard.COLLECTIVES_AT_WORLD_ONE = True  # run the RCCL path although the world has one rank
 
@@ -54,9 +54,9 @@ print("rccl child ok")
 
 
 def test_rccl_world1_equals_no_collectives(tmp_path):
-    import test_gpu_batch_renderer as t
-
     import torch
+
+    import renderer_fixtures as t
 
     torch.manual_seed(100)
     t._step((0, 1), 5, str(tmp_path), "plain")  # the same step without a process group

@@ -1,11 +1,12 @@
 """The fused SuGaR kernels on the GPU against fixtures computed by the reference's own code (tests/golden/*.npz, made by
-tests/golden/make_golden.py; what is lifted and how: tests/test_reference_pins.py, which pins the torch restatements
-to the same fixtures on the CPU).
+tests/golden/make_golden.py and read by ``fixture`` of tests/sugar_cases.py; what is lifted and how:
+tests/test_reference_pins.py, which pins the torch restatements to the same fixtures on the CPU).
 
-Bar, the one of tests/test_gpu_sugar_dynamic.py and tests/test_gpu_sugar_arap.py (their ``_rel``, ``_check`` and energy
-rule are imported, not copied): per tensor max |gpu - ref_f64| / max |ref_f64| <= 2 x the same figure of ``*_f32``
-against ``*_f64``, both read from the fixture, so the null is the reference's own float32 run; exact zeros where the
-reference tensor is all zero; per frame of the ARAP energy max(2 x null, 2^-23).  Each check prints its two figures.
+Bar, the one of the geometry stages' own GPU tests (``_rel`` and ``check_against_null`` of tests/sugar_cases.py and the
+energy rule, ``check_arap`` of tests/sugar_arap_reference.py, are imported, not copied): per tensor
+max |gpu - ref_f64| / max |ref_f64| <= 2 x the same figure of ``*_f32`` against ``*_f64``, both read from the fixture,
+so the null is the reference's own float32 run; exact zeros where the reference tensor is all zero; per frame of the
+ARAP energy max(2 x null, 2^-23).  Each check prints its two figures.
 Inputs stored in float64 (the unit quaternions) reach the kernels rounded to float32, as they reached the reference's
 float32 run.
 """
@@ -14,10 +15,11 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import sugar_mesh_reference as mesh_ref  # noqa: E402
-from test_gpu_sugar_arap import _check as check_arap  # noqa: E402
-from test_gpu_sugar_dynamic import _check, _rel  # noqa: E402
-from test_reference_pins import (ARAP_MESHES, FIELD_LEAVES, FIELD_RUNS, MESH_KEYS, SKIN_KEYS, TIMED_KEYS,  # noqa: E402
-                                 field_keys, fixture, mesh_fixture, tangent)
+from sugar_arap_reference import ARAP_MESHES, check_arap  # noqa: E402
+from sugar_cases import (FIELD_LEAVES, FIELD_RUNS, _rel, backprop, check_against_null, field_keys,  # noqa: E402
+                         fixture)
+from sugar_dynamic_reference import SKIN_KEYS, TIMED_KEYS, tangent  # noqa: E402
+from sugar_mesh_reference import MESH_KEYS, mesh_fixture  # noqa: E402
 
 F32 = torch.float32
 
@@ -44,8 +46,8 @@ def test_arap_energy(name, form):
     x = _leaf(z[f"{name}_xyz"])
     r = _leaf(z[f"{name}_rot"] if form == "matrix" else z[f"{name}_rot_q"])
     e = arap_energy(x, r, ArapBinding(z[f"{name}_verts"], z[f"{name}_faces"]).to("cuda"))
-    gx, gr = torch.autograd.grad((e * z[f"{name}_up"].to(F32).cuda()).sum(), [x, r])
-    check_arap({"energy": e.detach().cpu(), "dvert_xyz": gx.cpu(), "dvert_rot": gr.cpu()}, *refs, f"{name} {form}")
+    got = backprop([e], ["energy"], [x, r], ["dvert_xyz", "dvert_rot"], {"energy": z[f"{name}_up"].to(F32)}, ["energy"])
+    check_arap(got, *refs, f"{name} {form}")
 
 
 @pytest.mark.gpu
@@ -60,16 +62,13 @@ def test_skin_vertices(K, method):
     binding = SkinBinding(z[f"skin_K{K}_nbr"], z[f"skin_K{K}_w"], 7).to("cuda")
     leaves = [_leaf(z[k]) for k in ("skin_verts", "skin_node_trans", "skin_node_rots", "skin_node_scales")]
     out = skin_vertices(leaves[0], z["skin_node_xyz"].cuda(), leaves[1], leaves[2], binding, method, leaves[3])
-    names = ("xyz", "rotation", "scale")
-    loss = sum((o * z[f"skin_K{K}_up_{k}"].to(F32).cuda()).sum() for k, o in zip(names, out))
-    grads = torch.autograd.grad(loss, leaves)
-    got = {k: o.detach().cpu() for k, o in zip(names, out)}
-    got.update({k: g.cpu() for k, g in zip(SKIN_KEYS[3:], grads)})
+    names = SKIN_KEYS[:3]
+    got = backprop(out, names, leaves, SKIN_KEYS[3:], {k: z[f"skin_K{K}_up_{k}"].to(F32) for k in names}, names)
     r64, r32 = ({k: z[f"skin_K{K}_{method}_{k}_{tag}"] for k in SKIN_KEYS} for tag in ("f64", "f32"))
     if method == "lbs":
         for d in (got, r64, r32):
             d["dnode_rots"] = tangent(d["dnode_rots"], z["skin_node_rots"])
-    _check(got, r64, r32, SKIN_KEYS, f"skin K={K} {method}")
+    check_against_null(got, r64, r32, SKIN_KEYS, f"skin K={K} {method}")
 
 
 @pytest.mark.gpu
@@ -85,13 +84,11 @@ def test_timed_gaussians(G):
     thickness = float(z["timed_thickness"])
     xyz, rotation, normals, scaling = timed_gaussians(leaves[0], leaves[1], leaves[2], binding, leaves[3], leaves[4],
                                                       thickness)
-    out = {"xyz": xyz, "rotation": rotation, "scale": scaling}
-    loss = sum((o * z[f"timed_G{G}_up_{k}"].to(F32).cuda()).sum() for k, o in out.items())
-    grads = torch.autograd.grad(loss, leaves)
-    got = {k: o.detach().cpu() for k, o in out.items()}
-    got.update({k: g.cpu() for k, g in zip(TIMED_KEYS[3:], grads)})
+    names = TIMED_KEYS[:3]
+    got = backprop((xyz, rotation, scaling), names, leaves, TIMED_KEYS[3:],
+                   {k: z[f"timed_G{G}_up_{k}"].to(F32) for k in names}, names)
     r64, r32 = ({k: z[f"timed_G{G}_{k}_{tag}"] for k in TIMED_KEYS} for tag in ("f64", "f32"))
-    _check(got, r64, r32, TIMED_KEYS, f"timed G={G}")
+    check_against_null(got, r64, r32, TIMED_KEYS, f"timed G={G}")
     assert torch.equal(got["scale"][..., 0], torch.full(got["scale"].shape[:2], thickness, dtype=F32))
     assert torch.isfinite(normals).all()
 
@@ -108,14 +105,12 @@ def test_bound_gaussians(G):
     leaves = [_leaf(z[k]) for k in ("verts", f"G{G}_complex", f"G{G}_log_scales")]
     thickness = float(z["thickness"])
     out = bound_gaussians(*leaves, binding, thickness)
-    loss = sum((o * z[f"G{G}_up_{k}"].to(F32).cuda()).sum() for k, o in zip(mesh_ref.OUTPUTS, out))
-    grads = torch.autograd.grad(loss, leaves)
-    got = {k: o.detach().cpu() for k, o in zip(mesh_ref.OUTPUTS, out)}
-    got.update({k: g.cpu() for k, g in zip(mesh_ref.GRADS, grads)})
+    ups = {k: z[f"G{G}_up_{k}"].to(F32) for k in mesh_ref.OUTPUTS}
+    got = backprop(out, mesh_ref.OUTPUTS, leaves, mesh_ref.GRADS, ups, mesh_ref.OUTPUTS)
     r64, r32 = mesh_fixture(z, G, "f64"), mesh_fixture(z, G, "f32")
     for d in (got, r32):
         assert bool((mesh_ref.row_sign(d["rotation"], r64["rotation"]) > 0).all())
-    _check(got, r64, r32, MESH_KEYS, f"bound G={G}")
+    check_against_null(got, r64, r32, MESH_KEYS, f"bound G={G}")
     assert torch.equal(got["scaling"][:, 0], torch.full((20 * G,), thickness, dtype=F32))
     assert _rel(got["xyz"], r64["xyz"]) < 1e-6
 
@@ -152,14 +147,14 @@ def test_field_values(K, run):
         got.update({"d" + k: (torch.zeros_like(l) if g is None else g).cpu()
                     for (k, l), g in zip(leaves.items(), grads)})
     r64, r32 = ({k: z[f"K{K}_{run}_{k}_{tag}"] for k in keys} for tag in ("f64", "f32"))
-    _check(got, r64, r32, keys, f"field K={K} {run}")
+    check_against_null(got, r64, r32, keys, f"field K={K} {run}")
     if run == "a":  # the fused op by itself
         den, beta_avg, op = neighbor_density(leaves["x"], leaves["points"], leaves["inv_sr"], leaves["strengths"],
                                              leaves["scaling"].min(dim=-1)[0], density_factor=df,
                                              return_opacities=True, **index)
         direct = {"density": den.detach().cpu(), "beta": beta_avg.detach().cpu(),
                   "closest_gaussian_opacities": op.detach().cpu()}
-        _check(direct, r64, r32, tuple(direct), f"neighbor_density K={K}")
+        check_against_null(direct, r64, r32, tuple(direct), f"neighbor_density K={K}")
 
 
 @pytest.mark.gpu
@@ -180,5 +175,5 @@ def test_neighbor_normal_loss(K):
         loss = neighbor_normal_loss(z["x"].cuda(), z["points"].cuda(), normals, z["scaling"].min(-1)[0].cuda(),
                                     z[f"K{K}_a_closest_gaussian_opacities_f32"].cuda(), gaussian_idx=own, **table)
         (g,) = torch.autograd.grad((loss * z[f"K{K}_up_normal"].to(F32).cuda()).sum(), normals)
-        _check({"loss": loss.detach().cpu(), "dnormals": g.cpu()}, r64, r32, ("loss", "dnormals"),
-               f"normal K={K} {next(iter(table))}")
+        check_against_null({"loss": loss.detach().cpu(), "dnormals": g.cpu()}, r64, r32, ("loss", "dnormals"),
+                           f"normal K={K} {next(iter(table))}")

@@ -3,34 +3,14 @@ through its C-ABI entry gsr_sort_pairs, against numpy's stable sort (ADVICE r05:
 counts are read by every lane and advanced by each digit's first lane — many equal digits per wave, ragged segment
 tails, empty and one-item segments, full 4096-item blocks and bounded last blocks, keys-only and key/value, 4-, 6-
 and 8-bit digits and the runtime-width path).  Bit-exact: integer work."""
-import ctypes
-
 import numpy as np
 import pytest
+
+from gsr_testutil import gpu_sort_pairs as _sort
 
 pytestmark = pytest.mark.gpu
 
 SEGS = [0, 1, 63, 64, 4095, 4096, 4097, 12288, 20000 + 37, 0, 5]
-
-
-def _sort(keys, vals, sizes, key_bits, max_bits):
-    import torch
-
-    from diff_gaussian_rasterization import _C
-
-    lib = _C.load_library()
-    n = (ctypes.c_int * len(sizes))(*sizes)
-    k = torch.tensor(keys.view(np.int32), device="cuda")
-    v = torch.tensor(vals.view(np.int32), device="cuda") if vals is not None else None
-    wb = lib.gsr_sort_work_bytes(len(sizes), n)
-    assert wb > 0
-    work = torch.empty(wb, dtype=torch.uint8, device="cuda")
-    rc = lib.gsr_sort_pairs(len(sizes), n, ctypes.c_void_p(k.data_ptr()),
-                            ctypes.c_void_p(v.data_ptr()) if v is not None else None, key_bits, max_bits,
-                            ctypes.c_void_p(work.data_ptr()), wb, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0, lib.gsr_last_error()
-    torch.cuda.synchronize()
-    return k.cpu().numpy().view(np.uint32), (v.cpu().numpy().view(np.uint32) if v is not None else None)
 
 
 def _expect(keys, vals, sizes, key_bits):
@@ -100,8 +80,8 @@ def test_ballot_ranks_give_the_same_bits(tmp_path):
     np.save(tmp_path / "k.npy", keys)
     np.save(tmp_path / "v.npy", vals)
     code = (
-        "import sys, numpy as np; sys.path[:0] = [%r, %r]; import test_gpu_sort as t; from diff_gaussian_rasterization "
-        "import _C; k = np.load(%r); v = np.load(%r); gk, gv = t._sort(k, v, %r, 32, 6); "
+        "import sys, numpy as np; sys.path[:0] = [%r, %r]; import gsr_testutil as t; from diff_gaussian_rasterization "
+        "import _C; k = np.load(%r); v = np.load(%r); gk, gv = t.gpu_sort_pairs(k, v, %r, 32, 6); "
         "np.save(%r, gk); np.save(%r, gv); print(_C.load_library().gsr_sort_rank_mode())"
         % (os.path.dirname(os.path.abspath(__file__)),
            os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "threestudio-3dgs_amd"),

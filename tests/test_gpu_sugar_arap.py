@@ -2,17 +2,15 @@
 restatement of the reference's padded per-frame computation (tests/sugar_arap_reference.py), differentiated by
 autograd on the CPU.
 
-Bar, as in tests/test_gpu_sugar_dynamic.py.  Per gradient tensor: max |gpu - ref64| / max |ref64| <= 2 x the same
-figure of the restatement in float32 on the CPU (the "fp32 null", computed here on the same inputs); where the
-reference tensor is all zero the result must be exactly zero.  The (T,) energy has too few elements for the null to be
-a stable sample: per frame |gpu - ref64| / |ref64| <= max(2 x null, 2^-23), the second term being one float32 rounding
+Bar (``check_arap`` of tests/sugar_arap_reference.py).  Per gradient tensor the project's rule (``check_against_null``
+of tests/sugar_cases.py): at most twice the error of the restatement in float32 on the CPU (the "fp32 null", computed
+here on the same inputs), exact zeros where the reference is all zero.  The (T,) energy has too few elements for the
+null to be a stable sample: per frame |gpu - ref64| / |ref64| <= max(2 x null, 2^-23), the second term being one float32 rounding
 of an fp64 result, doubled.  Each check prints its figures.  The upstream gradient is a random weight per frame.
 Rest meshes have obtuse corners (negative weights: asserted); the deformed vertices are the rest vertices plus noise
 of the edge-length scale; quaternions have norms in [0.5, 1.5] and both signs of w (the matrix formula is not
 normalised); matrices are random, not rotations.
 """
-import functools
-
 import pytest
 
 torch = pytest.importorskip("torch")
@@ -20,34 +18,12 @@ torch = pytest.importorskip("torch")
 import gsr_synthetic as gs  # noqa: E402
 import sugar_arap_reference as ref  # noqa: E402
 import sugar_dynamic_reference as dyn_ref  # noqa: E402
-from sugar_cases import _rel, jittered_icosphere, mesh, random_quats  # noqa: E402
+from sugar_cases import NullCase, backprop, jittered_icosphere, mesh, random_quats  # noqa: E402
 
 FORMS = ("quat", "matrix")
-ENERGY_FLOOR = 2.0 ** -23
 
 
-def _check(got, r64, r32, tag):
-    for k in ("dvert_xyz", "dvert_rot"):
-        assert got[k].dtype == torch.float32 and got[k].shape == r64[k].shape, (tag, k, got[k].shape)
-        err, bar = _rel(got[k], r64[k]), 2 * _rel(r32[k], r64[k])
-        print(f"{tag} {k}: gpu {err:.3g}  fp32 null {bar / 2:.3g}")
-        if not r64[k].any():
-            assert not got[k].any(), (tag, k)
-        else:
-            assert torch.isfinite(got[k]).all() and err <= bar, (tag, k, err, bar)
-    e, e64, e32 = got["energy"].double(), r64["energy"], r32["energy"].double()
-    assert got["energy"].dtype == torch.float32 and e.shape == e64.shape, (tag, e.shape)
-    for t in range(len(e64)):
-        scale = abs(float(e64[t]))
-        if scale == 0:
-            assert float(e[t]) == 0, (tag, t)
-            continue
-        err, null = abs(float(e[t] - e64[t])) / scale, abs(float(e32[t] - e64[t])) / scale
-        print(f"{tag} energy[{t}]: gpu {err:.3g}  fp32 null {null:.3g}")
-        assert err <= max(2 * null, ENERGY_FLOOR), (tag, t, err, null)
-
-
-class _Case:
+class _Case(NullCase):
     """A rest mesh with random deformed vertices, rotations and upstream weights; reference and null computed once."""
 
     def __init__(self, name, T, form, seed=0):
@@ -60,25 +36,26 @@ class _Case:
         self.rings = ref.one_rings(self.faces, V)
         assert torch.equal(self.binding.nbr.long(), self.rings[1])
         assert bool((self.binding.w < 0).any())  # an obtuse corner
-        p = self.binding.p
-        edge = float(p.norm(dim=-1).mean())
+        edge = float(self.binding.p.norm(dim=-1).mean())
         self.xyz = self.verts[None] + 0.3 * edge * torch.randn(T, V, 3, generator=gen)
         self.rot = random_quats(gen, (T, V)) if form == "quat" else (
             torch.eye(3) + 0.4 * torch.randn(T, V, 3, 3, generator=gen))
         self.up = torch.randn(T, generator=gen)
+        self.ups = {"energy": self.up}
 
-    @functools.cached_property
-    def refs(self):
-        return tuple(ref.evaluate(dt, self.xyz, self.rot, self.verts, self.rings, self.binding.w, self.up)
-                     for dt in (torch.float64, torch.float32))
+    def evaluate(self, dtype, ups):
+        return ref.evaluate(dtype, self.xyz, self.rot, self.verts, self.rings, self.binding.w, ups["energy"])
 
     def gpu(self, up=None):
         from sugar_arap import arap_energy
 
         x, r = self.xyz.cuda().requires_grad_(), self.rot.cuda().requires_grad_()
         e = arap_energy(x, r, self.binding.to("cuda"))
-        gx, gr = torch.autograd.grad((e * (self.up if up is None else up).cuda()).sum(), [x, r])
-        return {"energy": e.detach().cpu(), "dvert_xyz": gx.cpu(), "dvert_rot": gr.cpu()}
+        ups = self.ups if up is None else {"energy": up}
+        return backprop([e], ["energy"], [x, r], ["dvert_xyz", "dvert_rot"], ups, ["energy"])
+
+    def check(self, got, tag):
+        ref.check_arap(got, *self.reference(self.outputs), tag)
 
 
 @pytest.mark.gpu
@@ -88,7 +65,7 @@ def test_small_meshes(name, T, form):
     """One triangle: every edge a boundary edge, W has one term each.  The tetrahedron is closed.  icosphere(1) has
     valences 5 and 6."""
     case = _Case(name, T, form, seed=1)
-    _check(case.gpu(), *case.refs, f"{name} T={T} {form}")
+    case.check(case.gpu(), f"{name} T={T} {form}")
 
 
 @pytest.mark.gpu
@@ -98,7 +75,7 @@ def test_icosphere3_has_several_block_sums(form):
     verts, faces = jittered_icosphere(3)
     case = _Case((torch.as_tensor(verts, dtype=torch.float32), torch.as_tensor(faces)), 2, form, seed=2)
     assert case.binding.n_verts == 642
-    _check(case.gpu(), *case.refs, f"icosphere(3) {form}")
+    case.check(case.gpu(), f"icosphere(3) {form}")
 
 
 @pytest.mark.gpu
@@ -109,7 +86,7 @@ def test_fan_of_200_faces(form):
     off = case.binding.offsets
     assert int(off[1] - off[0]) == 200 and case.binding.max_valence == 200 and int(off[-1] - off[-2]) == 0
     got = case.gpu()
-    _check(got, *case.refs, f"fan {form}")
+    case.check(got, f"fan {form}")
     for k in ("dvert_xyz", "dvert_rot"):
         assert not got[k][:, -1].any() and not torch.signbit(got[k][:, -1]).any(), k  # exactly 0.0
 
@@ -119,7 +96,7 @@ def test_fan_of_200_faces(form):
 def test_isolated_vertex_and_degenerate_face(form):
     case = _Case("isolated_degenerate", 2, form, seed=4)
     got = case.gpu()
-    _check(got, *case.refs, f"isolated + degenerate {form}")
+    case.check(got, f"isolated + degenerate {form}")
     for k in ("dvert_xyz", "dvert_rot"):
         assert not got[k][:, 12].any() and not torch.signbit(got[k][:, 12]).any(), k  # the empty row: exactly 0.0
         assert got[k][:, 13:].any(), k  # the clamped face's weights are finite and act
@@ -208,14 +185,6 @@ def test_chain_from_the_skinning(method):
     xyz, rot, _ = skin_vertices(verts.cuda(), node_xyz.cuda(), t, q, sb.to("cuda"), method)
     e = arap_energy(xyz, rot, ab.to("cuda"))
     gt, gq = torch.autograd.grad((e * up.cuda()).sum(), [t, q])
-    e = e.detach().cpu()
-    for k, g in (("dnode_trans", gt), ("dnode_rots", gq)):
-        err, bar = _rel(g.cpu(), r64[k]), 2 * _rel(r32[k], r64[k])
-        print(f"chain {method} {k}: gpu {err:.3g}  fp32 null {bar / 2:.3g}")
-        assert r64[k].any() and torch.isfinite(g).all() and err <= bar, (k, err, bar)
-    for i in range(T):
-        scale = abs(float(r64["energy"][i]))
-        err = abs(float(e[i]) - float(r64["energy"][i])) / scale
-        null = abs(float(r32["energy"][i]) - float(r64["energy"][i])) / scale
-        print(f"chain {method} energy[{i}]: gpu {err:.3g}  fp32 null {null:.3g}")
-        assert err <= max(2 * null, ENERGY_FLOOR), (i, err, null)
+    got = {"energy": e.detach().cpu(), "dnode_trans": gt.cpu(), "dnode_rots": gq.cpu()}
+    assert r64["dnode_trans"].any() and r64["dnode_rots"].any()
+    ref.check_arap(got, r64, r32, f"chain {method}", grads=("dnode_trans", "dnode_rots"))

@@ -3,9 +3,8 @@ torch restatement of the same formulas (tests/sugar_deform_reference.py, pinned 
 DeformationNetwork by tests/test_sugar_deform.py), differentiated by autograd on the CPU, and against the reference's
 fixture itself.
 
-Bar, the project's rule (``_check`` of tests/test_gpu_sugar_dynamic.py, imported): per tensor max |gpu - ref64| /
-max |ref64| <= 2 x the same figure of the restatement in float32 on the CPU (the "fp32 null", computed here on the same
-inputs); where the reference tensor is all zero the result must be exactly zero.  Each check prints its figures.
+Bar, the project's rule (``check_against_null`` of tests/sugar_cases.py, which states it): at most twice the error of
+the restatement in float32 on the CPU (the "fp32 null", computed here on the same inputs).  Every check prints both.
 Small planes (resolution (4, 5, 6, 3), multires (1, 2)) unless stated; random planes, MLP and upstream gradients.
 """
 import pytest
@@ -13,7 +12,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import sugar_deform_reference as ref  # noqa: E402
-from test_gpu_sugar_dynamic import _check  # noqa: E402
+from sugar_cases import NullCase, backprop, check_against_null  # noqa: E402
 
 F32 = torch.float32
 RESOLUTION, MULTIRES = (4, 5, 6, 3), (1, 2)
@@ -33,7 +32,7 @@ def random_weights(gen, resolution=RESOLUTION, multires=MULTIRES, d_scale=True):
     return w
 
 
-class _Deform:
+class _Deform(NullCase):
     """Points, ticks, weights and upstream gradients; reference and null computed once per set of gradients."""
 
     def __init__(self, points, ticks, weights, normalize=True, d_scale=True, seed=0, resolution=RESOLUTION,
@@ -48,34 +47,19 @@ class _Deform:
         if d_scale:
             self.ups["scale"] = torch.randn(T, P, 3, generator=gen)
         self.keys = ref.keys(len(weights.planes), len(self.mlp))
-        self._refs = {}
 
-    def reference(self, which):
-        if which not in self._refs:
-            ups = {k: self.ups[k] for k in which}
-            self._refs[which] = tuple(ref.evaluate(dt, self.points, self.ticks, AABB, self.w.planes, self.mlp, ups,
-                                                   self.normalize) for dt in (torch.float64, F32))
-        return self._refs[which]
+    def evaluate(self, dtype, ups):
+        return ref.evaluate(dtype, self.points, self.ticks, AABB, self.w.planes, self.mlp, ups, self.normalize)
 
     def gpu(self, which=None):
         from sugar_deform import HexPlaneBinding, deformation_knots
 
-        which = tuple(self.ups) if which is None else which
         binding = HexPlaneBinding(self.points, self.ticks, AABB, self.resolution, self.multires).to("cuda")
         w = self.w.to("cuda").requires_grad_()
         out = deformation_knots(binding, w, self.normalize, self.d_scale)
         assert (out[2] is None) == (not self.d_scale)
-        loss = sum((o * self.ups[k].cuda()).sum() for k, o in zip(ref.OUTPUTS, out) if k in which)
-        leaves = w.planes + w.mlp[:len(self.mlp)]
-        grads = torch.autograd.grad(loss, leaves)
-        got = {k: o.detach().cpu() for k, o in zip(ref.OUTPUTS, out) if o is not None}
-        got.update({k: g.cpu() for k, g in zip(self.keys[len(got):], grads)})
-        return got
-
-    def check(self, got, which=None, tag=""):
-        which = tuple(self.ups) if which is None else tuple(which)
-        r64, r32 = self.reference(which)
-        _check(got, r64, r32, self.keys, tag)
+        return backprop(out, ref.OUTPUTS, w.planes + w.mlp[:len(self.mlp)], self.keys[len(self.ups):], self.ups,
+                        which or self.outputs)
 
 
 def _points(P, gen, spread=1.3):
@@ -201,23 +185,19 @@ def test_bitwise_repeatable():
 def test_reference_fixture(case):
     """The reference's own DeformationNetwork (tests/golden/reference_deform.npz): the null is its float32 run."""
     from sugar_deform import HexPlaneBinding, deformation_knots
-    from test_sugar_deform import CASES, fixture, fixture_reference, fixture_ups, fixture_weights
 
-    z = fixture()
-    normalize, d_scale = CASES[case]
-    w = fixture_weights(z, d_scale)
-    r64, r32 = (fixture_reference(z, case, tag, w) for tag in ("f64", "f32"))
+    z = ref.fixture()
+    normalize, d_scale = ref.CASES[case]
+    w = ref.fixture_weights(z, d_scale)
+    r64, r32 = (ref.fixture_reference(z, case, tag, w) for tag in ("f64", "f32"))
     binding = HexPlaneBinding(z["points"], z["ticks"], z["aabb"], RESOLUTION, MULTIRES).to("cuda")
     wg = w.to("cuda").requires_grad_()
     out = deformation_knots(binding, wg, normalize, d_scale)
-    ups = fixture_ups(z, d_scale)
-    loss = sum((o * ups[k].to(F32).cuda()).sum() for k, o in zip(ref.OUTPUTS, out) if o is not None)
-    grads = torch.autograd.grad(loss, wg.parameters())
-    got = {k: o.detach().cpu() for k, o in zip(ref.OUTPUTS, out) if o is not None}
-    got.update({k: g.cpu() for k, g in zip(ref.keys(12, len(w.mlp))[len(got):], grads)})
+    ups = {k: up.to(F32) for k, up in ref.fixture_ups(z, d_scale).items()}
+    got = backprop(out, ref.OUTPUTS, wg.parameters(), ref.keys(12, len(w.mlp))[len(ups):], ups, tuple(ups))
     keys = tuple(k for k in got if k in r64)
     assert len(keys) == {"dg": 29, "dg_noscale": 11, "vert": 15}[case]
-    _check(got, r64, r32, keys, f"fixture {case}")
+    check_against_null(got, r64, r32, keys, f"fixture {case}")
 
 
 @pytest.mark.gpu
@@ -276,8 +256,5 @@ def test_chain_to_the_skinned_vertices():
     kx, kr, ks = deformation_knots(binding, wg)
     nt, nr, ns = spline_attributes(t.cuda(), kx, kr, grid, ks)
     out = skin_vertices(verts.cuda(), node_xyz.cuda(), nt, nr, sb.to("cuda"), "dqs", ns)
-    loss = sum((o * ups[k].cuda()).sum() for k, o in zip(names, out))
-    grads = torch.autograd.grad(loss, wg.parameters())
-    got = {k: o.detach().cpu() for k, o in zip(names, out)}
-    got.update({k: g.cpu() for k, g in zip(keys[3:], grads)})
-    _check(got, r64, r32, keys, "deform -> spline -> skin")
+    got = backprop(out, names, wg.parameters(), keys[3:], ups, names)
+    check_against_null(got, r64, r32, keys, "deform -> spline -> skin")

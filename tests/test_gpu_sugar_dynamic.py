@@ -2,8 +2,8 @@
 csrc/gsr_dynamic.hip) on the GPU against the fp64 torch restatement of the same formulas
 (tests/sugar_dynamic_reference.py), differentiated by autograd on the CPU.
 
-Bar, as in tests/test_gpu_sugar_mesh.py.  Per tensor (the outputs, the gradients): max |gpu - ref64| / max |ref64|
-<= 2 x the same figure of the restatement in float32 on the CPU (the "fp32 null", computed here on the same inputs):
+Bar (``check_against_null`` of tests/sugar_cases.py), as in tests/test_gpu_sugar_mesh.py.  Per tensor (the outputs, the
+gradients): max |gpu - ref64| / max |ref64| <= 2 x the same figure of the restatement in float32 on the CPU (the "fp32 null", computed here on the same inputs):
 the kernels may not be less exact than twice what they replace; the factor 2 is there because the null is itself a few
 ulps of one rounding sample.  Where the reference tensor is all zero the result must be exactly zero.  No quaternion
 sign alignment: Exp yields w >= 0 and the product is deterministic.  Each check prints its figures.
@@ -19,23 +19,12 @@ torch = pytest.importorskip("torch")
 
 import gsr_synthetic as gs  # noqa: E402
 import sugar_dynamic_reference as ref  # noqa: E402
-from sugar_cases import _fan, _rel, random_quats  # noqa: E402
+from sugar_cases import NullCase, _fan, _rel, backprop, random_quats  # noqa: E402
 
 THICKNESS = 3.5e-6
 
 
-def _check(got, r64, r32, keys, tag):
-    for k in keys:
-        assert got[k].dtype == torch.float32 and got[k].shape == r64[k].shape, (tag, k, got[k].shape)
-        err, bar = _rel(got[k], r64[k]), 2 * _rel(r32[k], r64[k])
-        print(f"{tag} {k}: gpu {err:.3g}  fp32 null {bar / 2:.3g}")
-        if not r64[k].any():
-            assert not got[k].any(), (tag, k)  # nothing contributes: exactly zero
-        else:
-            assert torch.isfinite(got[k]).all() and err <= bar, (tag, k, err, bar)
-
-
-class _Skin:
+class _Skin(NullCase):
     """A deformation graph with random node attributes and upstream gradients; reference and null computed once."""
 
     def __init__(self, T, verts, P, K, method, scales, seed=0, nbr=None, identity=False):
@@ -61,38 +50,22 @@ class _Skin:
         self.ups = {"xyz": torch.randn(T, V, 3, generator=gen), "rot": torch.randn(T, V, 4, generator=gen)}
         if scales:
             self.ups["scale"] = torch.randn(T, V, 3, generator=gen)
-        self.outputs = tuple(self.ups)
         self.keys = self.outputs + ("dverts", "dnode_trans", "dnode_rots") + (("dnode_scales",) if scales else ())
-        self._refs = {}
 
-    def reference(self, which):
-        if which not in self._refs:
-            ups = {k: self.ups[k] for k in which}
-            inputs = dict(verts=self.verts, node_trans=self.trans, node_rots=self.rots, node_scales=self.scales)
-            b = self.binding
-            self._refs[which] = tuple(ref.evaluate_skin(dt, inputs, self.node_xyz, b.nbr, b.w, self.method, ups)
-                                      for dt in (torch.float64, torch.float32))
-        return self._refs[which]
+    def evaluate(self, dtype, ups):
+        inputs = dict(verts=self.verts, node_trans=self.trans, node_rots=self.rots, node_scales=self.scales)
+        return ref.evaluate_skin(dtype, inputs, self.node_xyz, self.binding.nbr, self.binding.w, self.method, ups)
 
     def gpu(self, which=None):
         from sugar_dynamic import skin_vertices
 
-        which = self.outputs if which is None else which
         leaves = [None if t is None else t.cuda().requires_grad_()
                   for t in (self.verts, self.trans, self.rots, self.scales)]
         out = skin_vertices(leaves[0], self.node_xyz.cuda(), leaves[1], leaves[2], self.binding.to("cuda"),
                             self.method, leaves[3])
         assert (out[2] is None) == (self.scales is None)
-        loss = sum((o * self.ups[k].cuda()).sum() for k, o in zip(ref.SKIN_OUTPUTS, out) if k in which)
-        grads = torch.autograd.grad(loss, [t for t in leaves if t is not None])
-        got = {k: v.detach().cpu() for k, v in zip(ref.SKIN_OUTPUTS, out) if v is not None}
-        got.update({"d" + k: g.cpu() for k, g in zip(ref.SKIN_INPUTS, grads)})
-        return got
-
-    def check(self, got, which=None, tag=""):
-        which = self.outputs if which is None else tuple(which)
-        r64, r32 = self.reference(which)
-        _check(got, r64, r32, self.keys, tag)
+        return backprop(out, ref.SKIN_OUTPUTS, leaves, ["d" + k for k in ref.SKIN_INPUTS], self.ups,
+                        which or self.outputs)
 
 
 @functools.lru_cache(maxsize=None)
@@ -176,7 +149,7 @@ def test_skin_bitwise_repeatable(method):
         assert torch.equal(a[k], b[k]), k
 
 
-class _Timed:
+class _Timed(NullCase):
     """A mesh with random deformed vertices, vertex rotations and upstream gradients."""
 
     def __init__(self, T, verts, faces, G, scales, seed=0):
@@ -198,37 +171,24 @@ class _Timed:
         if scales:
             self.ups["scaling"] = torch.randn(T, N, 3, generator=gen)
         self.scales = scales
-        self.outputs = tuple(self.ups)
         self.keys = self.outputs + tuple("d" + k for k in ref.TIMED_INPUTS if self.inputs[k] is not None)
-        self._refs = {}
 
-    def reference(self, which):
-        if which not in self._refs:
-            ups = {k: self.ups[k] for k in which}
-            self._refs[which] = tuple(ref.evaluate_timed(dt, self.inputs, self.faces, self.binding.bary, THICKNESS,
-                                                         ups) for dt in (torch.float64, torch.float32))
-        return self._refs[which]
+    def evaluate(self, dtype, ups):
+        return ref.evaluate_timed(dtype, self.inputs, self.faces, self.binding.bary, THICKNESS, ups)
 
     def gpu(self, which=None):
         from sugar_dynamic import timed_gaussians
 
-        which = self.outputs if which is None else which
         leaves = {k: None if t is None else t.cuda().requires_grad_() for k, t in self.inputs.items()}
         opt = dict(vert_scale=leaves["vert_scale"], log_scales=leaves["log_scales"], thickness=THICKNESS)
         out = timed_gaussians(leaves["vert_xyz"], leaves["vert_rot"], leaves["rotation0"], self.binding.to("cuda"),
                               **(opt if self.scales else {}))
         assert (out[3] is None) == (not self.scales)
-        loss = sum((o * self.ups[k].cuda()).sum() for k, o in zip(ref.TIMED_OUTPUTS, out) if k in which)
-        have = [k for k in ref.TIMED_INPUTS if leaves[k] is not None]
-        grads = torch.autograd.grad(loss, [leaves[k] for k in have])
-        got = {k: v.detach().cpu() for k, v in zip(ref.TIMED_OUTPUTS, out) if v is not None}
-        got.update({"d" + k: g.cpu() for k, g in zip(have, grads)})
-        return got
+        return backprop(out, ref.TIMED_OUTPUTS, [leaves[k] for k in ref.TIMED_INPUTS],
+                        ["d" + k for k in ref.TIMED_INPUTS], self.ups, which or self.outputs)
 
     def check(self, got, which=None, tag=""):
-        which = self.outputs if which is None else tuple(which)
-        r64, r32 = self.reference(which)
-        _check(got, r64, r32, self.keys, tag)
+        super().check(got, which, tag)
         if self.scales:
             T, N = got["scaling"].shape[:2]
             assert torch.equal(got["scaling"][..., 0], torch.full((T, N), THICKNESS, dtype=torch.float32)), tag
@@ -357,10 +317,9 @@ def test_chain_feeds_the_rasterizer():
     given its frame's Gaussians, the normals as the second colour set.  It renders, and finite non-zero gradients
     reach node_trans and node_rots."""
     from diff_gaussian_rasterization.batched import rasterize_views
-    from gsr_testutil import make_camera
+    from gsr_testutil import _settings, make_camera
     from sugar_dynamic import SkinBinding, skin_vertices, timed_gaussians
     from sugar_mesh import MeshBinding, bound_gaussians, initial_log_scales
-    from test_gpu_configs import _settings
 
     dev = "cuda"
     v, f = gs.icosphere(3)

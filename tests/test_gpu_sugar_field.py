@@ -1,7 +1,8 @@
 """sugar_field.neighbor_density / get_field_values (include/gsr.h gsr_sugar_field_*, csrc/gsr_field.hip) on the GPU
 against an fp64 evaluation of the same formula.
 
-The checker (`_field`) is a short torch evaluation with autograd, on the CPU, over the fp32-rounded inputs:
+The checker (`_field` of tests/sugar_cases.py) is a short torch evaluation with autograd, on the CPU, over the
+fp32-rounded inputs:
     d = x_m - c_j,  w = A_j^T d,  q = clamp(w.w, 0, 1e8),  op = density_factor s_j exp(-q / 2),
     density = sum_k op,  beta_avg = (sum_k min_scale_j) / K,
 pairs whose index (or whose sample's row) is out of range masked to 0.  `_terms` restates every output element and
@@ -41,9 +42,8 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from sugar_cases import (EPS, M_FULL, N_REF, NAMES, _Case, _field, _full_case, _inputs, _mask, _scene,  # noqa: E402
-                         _terms)
-from sugar_cases import _quat_to_matrix, _run  # noqa: E402,F401  (for tests/test_reference_pins.py)
+from sugar_cases import (EPS, M_FULL, N_REF, NAMES, _Case, _compose64, _field, _full_case, _inputs,  # noqa: E402
+                         _mask, _scene, _terms)
 
 
 def _gpu(inp, ups, df=1.0, want_op=True, **index):
@@ -231,23 +231,6 @@ def _fields_inputs():
     x[1] = torch.tensor([50., 50., 50.])
     inp["x"] = x
     return inp, gi, idx
-
-
-def _compose64(density, op, beta_avg, ms_nb, mode, log_beta, threshold, clampv):
-    """The reference's remainder (utils/sugar_utils.py:313-341, 417-471) in fp64 from fp64 density / op / beta_avg."""
-    dens = density.clone()
-    m = dens >= 1.
-    dens[m] = dens[m] / (dens[m] + 1e-12)
-    if mode == "learnable":
-        beta = torch.exp(log_beta.double()).expand(len(density))
-    elif mode == "average":
-        beta = beta_avg
-    else:
-        osum = op.sum(-1, keepdim=True)
-        beta = (ms_nb * (op / osum.clamp(min=clampv))).sum(-1)
-        beta[osum[..., 0] == 0.] = ms_nb.max()
-    t = torch.sqrt(-2. * torch.log(dens.clamp(min=clampv)))
-    return dens, beta, t, beta * (t - math.sqrt(-2. * math.log(min(threshold, 1.))))
 
 
 @pytest.mark.gpu

@@ -1,10 +1,10 @@
 """sugar_mesh.bound_gaussians (include/gsr.h gsr_sugar_mesh_*, csrc/gsr_mesh.hip) on the GPU against the fp64 torch
 restatement of the same formulas (tests/sugar_mesh_reference.py), differentiated by autograd on the CPU.
 
-Bar.  Per tensor (the four outputs, the three gradients): max |gpu - ref64| / max |ref64| <= 2 x the same figure of the
-fp32 torch composition on the same inputs (the restatement in float32 on the CPU, the "fp32 null", computed here):
-the kernel may not be less exact than twice what it replaces.  The factor 2 is there because the null is itself a few
-ulps of one rounding sample.  Where the reference tensor is all zero the result must be exactly zero.  Before
+Bar (``check_against_null`` of tests/sugar_cases.py).  Per tensor (the four outputs, the three gradients):
+max |gpu - ref64| / max |ref64| <= 2 x the same figure of the restatement in float32 on the CPU (the "fp32 null",
+computed here on the same inputs): the kernel may not be less exact than twice what it replaces.  The factor 2 is there
+because the null is itself a few ulps of one rounding sample.  An all-zero reference tensor wants exact zeros.  Before
 comparing, each quaternion row's sign is aligned with the sign of its dot product with the reference row (the kernel
 and the reference may take different candidate rows of matrix_to_quaternion where two tie), and that row's upstream
 gradient is multiplied by the same sign, on the null's side too.  The thickness column of `scaling` and the gradients
@@ -20,12 +20,12 @@ torch = pytest.importorskip("torch")
 
 import gsr_synthetic as gs  # noqa: E402
 import sugar_mesh_reference as ref  # noqa: E402
-from sugar_cases import _fan, _rel  # noqa: E402
+from sugar_cases import NullCase, _fan, backprop, check_against_null  # noqa: E402
 
 THICKNESS = 3.5e-6
 
 
-class _Case:
+class _Case(NullCase):
     """A mesh with random per-Gaussian parameters and upstream gradients; the reference and the null computed once."""
 
     def __init__(self, verts, faces, G, seed=0, bary=None):
@@ -42,56 +42,38 @@ class _Case:
         self.cplx = torch.randn(N, 2, generator=gen)
         self.log_scales = torch.randn(N, 2, generator=gen) * 0.3 - 4
         self.ups = {k: torch.randn(N, 4 if k == "rotation" else 3, generator=gen) for k in ref.OUTPUTS}
-        self._refs = {}
+        self.keys = ref.OUTPUTS + ref.GRADS
 
     def evaluate(self, dtype, ups, sign=None):
         return ref.evaluate(dtype, self.verts, self.faces, self.binding.bary, self.cplx, self.log_scales, THICKNESS,
                             ups, sign=sign)
 
-    def reference(self, which):
-        """(fp64 reference without alignment, fp32 null, its row signs, the reference aligned to the null) for the
-        upstream gradients named in `which`."""
-        if which not in self._refs:
-            ups = {k: self.ups[k] for k in which}
-            r0 = self.evaluate(torch.float64, ups)
-            null = self.evaluate(torch.float32, ups)
-            sn = ref.row_sign(null["rotation"], r0["rotation"])
-            rn = r0 if bool((sn > 0).all()) else self.evaluate(torch.float64, ups, sign=sn)
-            self._refs[which] = (r0, null, sn, rn)
-        return self._refs[which]
+    def aligned(self, r0, got, ups):
+        """(row signs s of got's quaternions against r0's, the fp64 reference for them, its rows times s).  `got` had
+        the plain upstream gradient: a flipped row's reference gradient is that of -q, i.e. the reference with that
+        row's upstream gradient negated.  |got - s r| = |s got - r|, and the bar sees `got` as the kernel wrote it."""
+        s = ref.row_sign(got["rotation"], r0["rotation"])
+        r = r0 if bool((s > 0).all()) else self.evaluate(torch.float64, ups, sign=s)
+        return s, dict(r, rotation=r["rotation"] * s[:, None])
+
+    def references(self, ups):
+        """(fp64 reference without alignment, fp32 null, the reference aligned to the null)."""
+        r0, null = super().references(ups)
+        return r0, null, self.aligned(r0, null, ups)[1]
 
     def gpu(self, which=ref.OUTPUTS, binding=None):
         from sugar_mesh import bound_gaussians
 
         leaves = [t.cuda().requires_grad_() for t in (self.verts, self.cplx, self.log_scales)]
         out = bound_gaussians(*leaves, (binding or self.binding).to("cuda"), THICKNESS)
-        loss = sum((o * self.ups[k].cuda()).sum() for k, o in zip(ref.OUTPUTS, out) if k in which)
-        grads = torch.autograd.grad(loss, leaves)
-        got = {k: v.detach().cpu() for k, v in zip(ref.OUTPUTS, out)}
-        got.update({k: g.cpu() for k, g in zip(ref.GRADS, grads)})
-        return got
+        return backprop(out, ref.OUTPUTS, leaves, ref.GRADS, self.ups, which)
 
     def check(self, got, which=ref.OUTPUTS, tag=""):
-        which = tuple(which)
-        r0, null, sn, rn = self.reference(which)
-        s = ref.row_sign(got["rotation"], r0["rotation"])
-        r = r0
-        if not bool((s > 0).all()):
-            # the GPU result was computed with the plain upstream gradient: a flipped row's reference gradient is
-            # that of -q, i.e. the reference with that row's upstream gradient negated
-            r = self.evaluate(torch.float64, {k: self.ups[k] for k in which}, sign=s)
+        r0, null, rn = self.reference(tuple(which))
+        s, r = self.aligned(r0, got, {k: self.ups[k] for k in which})
         N = self.binding.n_gaussians
         assert torch.equal(got["scaling"][:, 0], torch.full((N,), THICKNESS, dtype=torch.float32)), tag
-        for k in ref.OUTPUTS + ref.GRADS:
-            assert got[k].dtype == torch.float32 and got[k].shape == r[k].shape, (tag, k, got[k].shape)
-            a = got[k] * s[:, None].float() if k == "rotation" else got[k]
-            n = null[k] * sn[:, None].float() if k == "rotation" else null[k]
-            err, bar = _rel(a, r[k]), 2 * _rel(n, rn[k])
-            print(f"{tag} {k}: gpu {err:.3g}  fp32 null {bar / 2:.3g}  flipped rows {int((s < 0).sum())}")
-            if not r[k].any():
-                assert not got[k].any(), (tag, k)  # nothing contributes: exactly zero
-            else:
-                assert torch.isfinite(got[k]).all() and err <= bar, (tag, k, err, bar)
+        check_against_null(got, r, null, self.keys, tag, null_ref=rn, note=f"  flipped rows {int((s < 0).sum())}")
 
 
 def _icosphere_case(subdiv, G):
@@ -234,9 +216,8 @@ def test_outputs_feed_the_sugar_normal_render():
     """icosphere(3)'s bound Gaussians through rasterize_views in the SuGaR normal renderer's form (the face normals
     as the second colour set), one 64 x 64 view: it renders, and the gradient reaches the vertices."""
     from diff_gaussian_rasterization.batched import rasterize_views
-    from gsr_testutil import make_camera
+    from gsr_testutil import _settings, make_camera
     from sugar_mesh import bound_gaussians, initial_log_scales
-    from test_gpu_configs import _settings
 
     case = _ico3()
     dev = "cuda"

@@ -1,8 +1,8 @@
 """sugar_field.neighbor_normal_loss / coarse_density_regulation (include/gsr.h gsr_sugar_normal_*, csrc/gsr_normal.hip)
 on the GPU against an fp64 evaluation of the same formula.
 
-The checker (`_normal`) is the reference's composition (utils/sugar_utils.py:726-757) in torch with autograd, on the
-CPU, over the fp32-rounded inputs:
+The checker (`_normal` of tests/sugar_cases.py) is the reference's composition (utils/sugar_utils.py:726-757) in torch
+with autograd, on the CPU, over the fp32-rounded inputs:
     s = sign(n_j . n_i),  a = |(x - c_j) . (s n_j)|,  w = op a / max(ms_j, 1e-6)^2,  W = sum_k w,
     wh = w / max(W, 1e-6),  r = n_i - sum_k wh s n_j,  loss = r . r,
 with s, a and W detached (gradients reach the normals only), pairs whose index is out of range masked to 0 and the
@@ -66,9 +66,9 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from sugar_cases import EPS, M_FULL, N_EXTRA, N_REF, _field, _mask, _ratios, _scene  # noqa: E402
+from sugar_cases import (EPS, M_FULL, N_EXTRA, N_REF, WMIN, _field, _mask, _normal, _ratios,  # noqa: E402
+                         _scene)
 
-WMIN = 1e-6
 DENORM = 2.0 ** -149  # the spacing of fp32 below 2^-126
 
 
@@ -91,34 +91,6 @@ def _inputs(M=M_FULL, K=16):
                op=ex["op"][:M, :K].contiguous())
     own = sc["gi"][:M]
     return inp, own, sc["knn"][own][:, :K].contiguous(), sc["g_density"][:M]
-
-
-def _normal(dtype, inp, idx, own, ok, own_ok, g, literal=False):
-    """loss (M,), dL/dnormals (N, 3), and the intermediates, of the reference's composition in `dtype`.  `literal`:
-    r summed as the reference writes it, n_i - sum_k wh s n_j (the fp32 null); otherwise in the equal arrangement
-    (1 - W / Wc) n_i + sum_k wh (n_i - s n_j), which does not cancel n_i against the sample's own slot (the fp64
-    checker: see the module docstring)."""
-    x, c, ms, op = (inp[k].to(dtype) for k in ("x", "centers", "min_scale", "op"))
-    nrm = inp["normals"].to(dtype).clone().requires_grad_()
-    n = c.shape[0]
-    j = idx.clamp(0, max(n - 1, 0))
-    ni = nrm[own.clamp(0, max(n - 1, 0))]
-    nj = nrm[j]
-    dot = (nj * ni[:, None]).sum(dim=-1, keepdim=True)
-    njs = nj * torch.sign(dot).detach()
-    a = ((x[:, None] - c[j]) * njs).sum(dim=-1).abs().detach()
-    w = op * a / ms[j].clamp(min=1e-6) ** 2 * ok
-    W = w.sum(dim=-1).detach()
-    wh = w / W.unsqueeze(-1).clamp(min=WMIN)
-    if literal:
-        r = ni - (wh[..., None] * njs).sum(dim=-2)
-    else:
-        rest = torch.where(W >= WMIN, torch.zeros_like(W), 1 - W / W.clamp(min=WMIN))
-        r = rest[:, None] * ni + (wh[..., None] * (ni[:, None] - njs)).sum(dim=-2)
-    loss = r.pow(2).sum(dim=-1) * own_ok
-    grad, = torch.autograd.grad((loss * g.to(dtype)).sum(), nrm) if len(loss) else (torch.zeros_like(nrm),)
-    return dict(loss=loss.detach(), dnormals=grad, r=r.detach(), wh=wh.detach(), s=torch.sign(dot).detach()[..., 0],
-                dot=dot.detach()[..., 0], W=W, nj=nj.detach(), ni=ni.detach(), j=j)
 
 
 class _Case:

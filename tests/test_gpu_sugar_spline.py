@@ -2,9 +2,8 @@
 torch restatement of the same formulas (tests/sugar_spline_reference.py, pinned to the reference's own Spline by
 tests/test_sugar_spline.py), differentiated by autograd on the CPU, and against the reference's fixture itself.
 
-Bar, the project's rule (``_check`` of tests/test_gpu_sugar_dynamic.py, imported): per tensor max |gpu - ref64| /
-max |ref64| <= 2 x the same figure of the restatement in float32 on the CPU (the "fp32 null", computed here on the same
-inputs); where the reference tensor is all zero the result must be exactly zero.  Each check prints its figures.
+Bar, the project's rule (``check_against_null`` of tests/sugar_cases.py, which states it): at most twice the error of
+the restatement in float32 on the CPU (the "fp32 null", computed here on the same inputs).  Every check prints both.
 Knot rotations keep the null itself away from Log's branch at theta = +-pi: angles within +-1.2 rad, so two adjacent
 knots are at most 2.4 rad apart; both signs of w, norms in [0.5, 1.5], some rows exactly the identity.
 """
@@ -15,14 +14,13 @@ torch = pytest.importorskip("torch")
 import gsr_synthetic as gs  # noqa: E402
 import sugar_dynamic_reference as dyn_ref  # noqa: E402
 import sugar_spline_reference as ref  # noqa: E402
-from sugar_cases import random_quats  # noqa: E402
-from test_gpu_sugar_dynamic import _check  # noqa: E402
+from sugar_cases import NullCase, backprop, check_against_null, random_quats  # noqa: E402
 
 F32 = torch.float32
 IDENTITY = [0.0, 0.0, 0.0, 1.0]
 
 
-class _Spline:
+class _Spline(NullCase):
     """Random knots, timestamps and upstream gradients; reference and null computed once per set of gradients."""
 
     def __init__(self, grid, timestamps, P, scales, seed=0, identity=False):
@@ -39,36 +37,19 @@ class _Spline:
         self.ups = {"xyz": torch.randn(T, P, 3, generator=gen), "rot": torch.randn(T, P, 4, generator=gen)}
         if scales:
             self.ups["scale"] = torch.randn(T, P, 3, generator=gen)
-        self.outputs = tuple(self.ups)
         self.keys = self.outputs + tuple("d" + k for k in ref.SPLINE_INPUTS if self.inputs[k] is not None)
-        self._refs = {}
 
-    def reference(self, which):
-        if which not in self._refs:
-            ups = {k: self.ups[k] for k in which}
-            self._refs[which] = tuple(ref.evaluate(dt, self.inputs, self.grid, self.t, ups)
-                                      for dt in (torch.float64, F32))
-        return self._refs[which]
+    def evaluate(self, dtype, ups):
+        return ref.evaluate(dtype, self.inputs, self.grid, self.t, ups)
 
     def gpu(self, which=None):
         from sugar_spline import spline_attributes
 
-        which = self.outputs if which is None else which
-        leaves = {k: None if t is None else t.cuda().requires_grad_() for k, t in self.inputs.items()}
-        out = spline_attributes(self.t.cuda(), leaves["knots_xyz"], leaves["knots_rot"], self.grid,
-                                leaves["knots_scale"])
+        leaves = [None if self.inputs[k] is None else self.inputs[k].cuda().requires_grad_() for k in ref.SPLINE_INPUTS]
+        out = spline_attributes(self.t.cuda(), leaves[0], leaves[1], self.grid, leaves[2])
         assert (out[2] is None) == (self.inputs["knots_scale"] is None)
-        loss = sum((o * self.ups[k].cuda()).sum() for k, o in zip(ref.SPLINE_OUTPUTS, out) if k in which)
-        have = [k for k in ref.SPLINE_INPUTS if leaves[k] is not None]
-        grads = torch.autograd.grad(loss, [leaves[k] for k in have])
-        got = {k: v.detach().cpu() for k, v in zip(ref.SPLINE_OUTPUTS, out) if v is not None}
-        got.update({"d" + k: g.cpu() for k, g in zip(have, grads)})
-        return got
-
-    def check(self, got, which=None, tag=""):
-        which = self.outputs if which is None else tuple(which)
-        r64, r32 = self.reference(which)
-        _check(got, r64, r32, self.keys, tag)
+        return backprop(out, ref.SPLINE_OUTPUTS, leaves, ["d" + k for k in ref.SPLINE_INPUTS], self.ups,
+                        which or self.outputs)
 
 
 def _grid(degree, n_knots=7):
@@ -172,24 +153,20 @@ def test_reference_fixture(degree, scale):
     """The reference's own Spline (tests/golden/reference_spline.npz), as tests/test_gpu_reference_pins.py compares the
     other stages: the null is the reference's float32 run.  The float64 unit quaternions reach the kernel rounded to
     float32, as they reached that run."""
+    from sugar_cases import fixture
     from sugar_spline import spline_attributes
-    from test_sugar_spline import SPLINE_KEYS, fixture, fixture_grid
 
     z = fixture("spline")
-    names = ("knots_xyz", "knots_rot") + (("knots_scale",) if scale else ())
-    leaves = [z[k].to(F32).cuda().requires_grad_() for k in names]
-    out = spline_attributes(z["timestamps"].cuda(), leaves[0], leaves[1], fixture_grid(z, degree),
-                            leaves[2] if scale else None)
+    leaves = [z[k].to(F32).cuda().requires_grad_() if scale or k != "knots_scale" else None for k in ref.SPLINE_INPUTS]
+    out = spline_attributes(z["timestamps"].cuda(), leaves[0], leaves[1], ref.fixture_grid(z, degree), leaves[2])
     assert (out[2] is None) == (not scale)
-    outs = {k: o for k, o in zip(("xyz", "rotation", "scale"), out) if o is not None}
-    loss = sum((o * z[f"up_{k}"].to(F32).cuda()).sum() for k, o in outs.items())
-    grads = torch.autograd.grad(loss, leaves)
-    got = {k: o.detach().cpu() for k, o in outs.items()}
-    got.update({"d" + k: g.cpu() for k, g in zip(names, grads)})
-    keys = tuple(k for k in SPLINE_KEYS if k in got)
+    names = ("xyz", "rotation", "scale")[:3 if scale else 2]
+    got = backprop(out, names, leaves, ["d" + k for k in ref.SPLINE_INPUTS], {k: z[f"up_{k}"].to(F32) for k in names},
+                   names)
+    keys = tuple(k for k in ref.SPLINE_KEYS if k in got)
     assert len(keys) == (6 if scale else 4)
     r64, r32 = ({k: z[f"deg{degree}_{k}_{tag}"] for k in keys} for tag in ("f64", "f32"))
-    _check(got, r64, r32, keys, f"fixture degree {degree} scale={scale}")
+    check_against_null(got, r64, r32, keys, f"fixture degree {degree} scale={scale}")
 
 
 @pytest.mark.gpu
@@ -237,8 +214,5 @@ def test_chain_to_the_timed_gaussians():
     nt, nr, ns = spline_attributes(t.cuda(), leaves["knots_xyz"], leaves["knots_rot"], grid, leaves["knots_scale"])
     vx, vr, vs = skin_vertices(verts.cuda(), node_xyz.cuda(), nt, nr, sb.to("cuda"), "dqs", ns)
     out = timed_gaussians(vx, vr, rotation0.cuda(), mb.to("cuda"), vs, log_scales.cuda(), thickness)
-    loss = sum((o * ups[k].cuda()).sum() for k, o in zip(names, out))
-    grads = torch.autograd.grad(loss, list(leaves.values()))
-    got = {k: o.detach().cpu() for k, o in zip(names, out)}
-    got.update({"d" + k: g.cpu() for k, g in zip(leaves, grads)})
-    _check(got, r64, r32, tuple(got), "spline -> skin -> timed")
+    got = backprop(out, names, leaves.values(), ["d" + k for k in leaves], ups, names)
+    check_against_null(got, r64, r32, tuple(got), "spline -> skin -> timed")

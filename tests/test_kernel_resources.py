@@ -3,16 +3,9 @@ has no VGPR spills to scratch beyond the two measured, documented trade-offs bel
 the backward blend's replay loop would cost a scratch round trip per pair).  Device-only
 compile with the Makefile's flags, no GPU needed.  SGPR spills are not checked: they land in VGPR
 lanes (v_writelane / v_readlane), not in scratch memory."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "threestudio-3dgs_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from kernel_budget import kernel_resources, needs_hipcc
 
 # mangled-name fragment -> VGPRs allowed to spill, each an occupancy choice measured on the GPU and
 # stated at the kernel's attribute: the two-colour per-Gaussian backward at 4 waves per SIMD spills outside the
@@ -25,25 +18,7 @@ ALLOWED_VGPR_SPILL = {"17k_render_fwd_tileILb0E": 0, "11k_view_gradILb1E": 4, "1
                       "13k_gauss_accum": 7}
 
 
-def kernel_resources(src, tmp_path):
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "--cuda-device-only",
-           "-c", src, "-o", str(tmp_path / "k.o"), "-Rpass-analysis=kernel-resource-usage"]
-    res = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stderr[-2000:]
-    out, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs Spill|SGPRs Spill|VGPRs|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name is not None:
-            out[name][m.group(1)] = int(m.group(2))
-    return out
-
-
-@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="hipcc not in this image")
+@needs_hipcc
 @pytest.mark.parametrize("src", ["gsr_render.hip", "gsr_backward.hip"])
 def test_hot_kernels_do_not_spill(src, tmp_path):
     res = kernel_resources(src, tmp_path)

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from diff_gaussian_rasterization import _C
+from kernel_budget import assert_kernel_budget, needs_hipcc
 
 RTOL = 1e-6
 KS = [1, 4, 16, 32]
@@ -162,20 +163,12 @@ def test_python_argument_errors():
         knn_points(p, K=4, lengths1=None)
 
 
+@needs_hipcc
 def test_knn_kernels_do_not_spill(tmp_path):
-    """Every list capacity keeps its list in registers (compiler resource remarks only)."""
-    import os
-    import shutil
-
-    from test_kernel_resources import HIPCC, kernel_resources
-
-    if not (os.path.exists(HIPCC) or shutil.which("hipcc")):
-        pytest.skip("hipcc not in this image")
-    res = {k: v for k, v in kernel_resources("gsr_knn.hip", tmp_path).items() if "k_knn" in k}
-    assert sum("k_knn_points" in k for k in res) == 4, sorted(res)  # capacities 4, 8, 16, 32
-    assert any("k_knn_query" in k for k in res)
-    for name, r in res.items():
-        assert r.get("VGPRs Spill", 0) == 0, (name, r)
+    """Every list capacity (4, 8, 16, 32) keeps its list in registers (compiler resource remarks only)."""
+    kernels = ("k_knn_bboxE", "k_knn_mortonE", "k_knn_gatherE", "k_knn_box_aabbE", "k_knn_aabbE", "k_knn_queryE",
+               "k_knn_pointsILi4E", "k_knn_pointsILi8E", "k_knn_pointsILi16E", "k_knn_pointsILi32E")
+    assert_kernel_budget("gsr_knn.hip", tmp_path, "k_knn", dict.fromkeys(kernels, 0))
 
 
 # ---------------------------------------------------------------------------------------------- GPU

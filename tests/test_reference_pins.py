@@ -1,6 +1,6 @@
 """Pin the torch restatements of the SuGaR stages (tests/sugar_arap_reference.py, tests/sugar_dynamic_reference.py,
-tests/sugar_mesh_reference.py, the field and normal checkers of tests/test_gpu_sugar_field.py and
-tests/test_gpu_sugar_normal.py), and the ArapBinding's weights, to fixtures computed by the reference's own code.
+tests/sugar_mesh_reference.py, the field and normal checkers of tests/sugar_cases.py), and the ArapBinding's weights, to
+fixtures computed by the reference's own code (read by ``fixture`` of tests/sugar_cases.py, which also holds the bars).
 
 tests/golden/make_golden.py lifts ARAPCoach (utils/arap_utils.py), the skinning / timed-Gaussian methods of
 geometry/dynamic_sugar.py with the DualQuaternion class (utils/dual_quaternions.py), and the mesh-bound property bodies
@@ -17,9 +17,6 @@ What the fixtures keep away from, on purpose: quaternions off the unit sphere (a
 rotations are float64 and unit to fp64 rounding), because what pypose's ``Log()`` and ``matrix()`` do there cannot be
 checked without pypose; see ``test_skin_restatement`` for the one place where that shows in a gradient.
 """
-import functools
-import os
-
 import numpy as np
 import pytest
 
@@ -28,43 +25,12 @@ torch = pytest.importorskip("torch")
 import sugar_arap_reference as arap_ref  # noqa: E402
 import sugar_dynamic_reference as dyn_ref  # noqa: E402
 import sugar_mesh_reference as mesh_ref  # noqa: E402
-
-GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
-D = torch.float64
-OUT_BAR, GRAD_BAR = 1e-12, 1e-10
-ARAP_MESHES = ("tetrahedron", "icosphere1", "fan40", "sliver")
-
-
-@functools.lru_cache(maxsize=None)
-def fixture(name):
-    with np.load(os.path.join(GOLDEN, f"reference_{name}.npz")) as z:
-        return {k: torch.from_numpy(z[k]) for k in z.files}
-
-
-def rel(a, b):
-    scale = float(b.double().abs().max()) if b.numel() else 0.0
-    return float((a.double() - b.double()).abs().max()) / scale if scale > 0 else 0.0
-
-
-def close(got, want, bar, tag):
-    assert got.dtype == want.dtype == D and got.shape == want.shape, (tag, got.dtype, got.shape, want.shape)
-    err = rel(got, want)
-    print(f"{tag}: {err:.3g} (bar {bar:g})")
-    if not want.any():
-        assert not got.any(), tag
-    else:
-        assert err <= bar, (tag, err, bar)
-
-
-def null_is_usable(z, prefix, keys):
-    """Every float32 tensor is finite, and differs from the float64 one (so 2 x the null is a bar, not zero), unless
-    the float64 tensor is all zero (then the GPU must give exact zeros)."""
-    for k in keys:
-        a, b = z[f"{prefix}{k}_f32"], z[f"{prefix}{k}_f64"]
-        assert a.dtype == torch.float32 and b.dtype == D and a.shape == b.shape, (prefix, k)
-        assert torch.isfinite(a).all() and torch.isfinite(b).all(), (prefix, k)
-        assert rel(a, b) > 0 or not b.any(), (prefix, k)
-
+from sugar_arap_reference import ARAP_MESHES  # noqa: E402
+from sugar_cases import (FIELD_RUNS, GRAD_BAR, OUT_BAR, D, _compose64, _field, _mask, _normal,  # noqa: E402
+                         _quat_to_matrix, _run, close, field_keys, fixture, null_is_usable)
+from sugar_cases import _rel as rel  # noqa: E402
+from sugar_dynamic_reference import SKIN_KEYS, TIMED_KEYS, tangent  # noqa: E402
+from sugar_mesh_reference import MESH_KEYS, mesh_fixture  # noqa: E402
 
 # ---------------------------------------------------------------------------------------------------------------------
 # the stand-ins against scipy
@@ -262,16 +228,6 @@ def test_arap_energy_at_rest_is_exactly_zero(name):
 # ---------------------------------------------------------------------------------------------------------------------
 # skinning and timed Gaussians
 
-SKIN_KEYS = ("xyz", "rotation", "scale", "dverts", "dnode_trans", "dnode_rots", "dnode_scales")
-TIMED_KEYS = ("xyz", "rotation", "scale", "dvert_xyz", "dvert_rot", "drotation0", "dvert_scale", "dlog_scales")
-
-
-def tangent(g, q):
-    """The part of a gradient g to unit quaternions q that is orthogonal to q: its component along q is the derivative
-    with respect to the quaternion's norm."""
-    q = q.to(g.dtype)
-    return g - (g * q).sum(-1, keepdim=True) * q
-
 
 def skin_restated(dtype, z, K, method):
     ups = {k: z[f"skin_K{K}_up_{n}"] for k, n in (("xyz", "xyz"), ("rot", "rotation"), ("scale", "scale"))}
@@ -363,17 +319,11 @@ def test_timed_restatement(G):
 # ---------------------------------------------------------------------------------------------------------------------
 # mesh-bound Gaussians
 
-MESH_KEYS = mesh_ref.OUTPUTS + mesh_ref.GRADS
-
 
 def mesh_restated(dtype, z, G, sign=None):
     ups = {k: z[f"G{G}_up_{k}"] for k in mesh_ref.OUTPUTS}
     return mesh_ref.evaluate(dtype, z["verts"], z["faces"], z[f"G{G}_bary"], z[f"G{G}_complex"], z[f"G{G}_log_scales"],
                              float(z["thickness"]), ups, sign=sign)
-
-
-def mesh_fixture(z, G, tag):
-    return {k: z[f"G{G}_{'d' if k in mesh_ref.GRADS else ''}{k}_{tag}"] for k in MESH_KEYS}
 
 
 @pytest.mark.parametrize("G", [1, 3])
@@ -411,16 +361,6 @@ def test_mesh_restatement(G):
 # ---------------------------------------------------------------------------------------------------------------------
 # density field and neighbour-normal loss
 
-FIELD_RUNS = {"a": ("average", 1.0, True, True), "w": ("weighted_average", 1.3, True, True),
-              "l": ("learnable", 1.0, False, False)}  # beta_mode, density_factor, return_sdf, opacities returned
-FIELD_LEAVES = ("x", "points", "inv_sr", "strengths", "scaling", "log_beta")
-
-
-def field_keys(run, grads=True):
-    mode, df, sdf_on, want_op = FIELD_RUNS[run]
-    keys = ("density", "beta") + (("sdf",) if sdf_on else ()) + (("closest_gaussian_opacities",) if want_op else ())
-    return keys + (tuple("d" + k for k in FIELD_LEAVES) if grads and run != "a" else ())
-
 
 def field_inputs(z, K, run):
     """The float32 tensors get_field_values was run on: Gaussians' inv_sr is the reference's own float32 one."""
@@ -456,12 +396,11 @@ def test_field_fixture_shapes_what_it_should():
 def test_covariance_and_smallest_axis_restated():
     """get_covariance (the inverse scaled rotation R(q) diag(1 / clamp(s, 1e-8)), the full matrix L L^T and its six
     upper entries) and get_smallest_axis against the short restatements the field and normal tests build their scenes
-    with (test_gpu_sugar_field._quat_to_matrix) and sugar_field.smallest_axis.  cov6 is float32 in the reference
+    with (sugar_cases._quat_to_matrix) and sugar_field.smallest_axis.  cov6 is float32 in the reference
     whatever the dtype of its inputs (``torch.zeros(..., dtype=torch.float)`` in get_covariance): the float64 run's
     cov6 is the float64 matrix rounded to float32, one float32 rounding: measured gap 3.0e-8 of the largest entry
     (2^-25); the bar is 4 x 2^-24, four times the format's bound for one rounding."""
     import sugar_field
-    from test_gpu_sugar_field import _quat_to_matrix
 
     z = fixture("field")
     Rm = _quat_to_matrix(z["quaternions"].double())
@@ -486,14 +425,12 @@ def test_covariance_and_smallest_axis_restated():
 @pytest.mark.parametrize("run", sorted(FIELD_RUNS))
 @pytest.mark.parametrize("K", [1, 16])
 def test_field_restatement(K, run):
-    """The field checker ``_field`` and the composition ``_compose64`` of tests/test_gpu_sugar_field.py in float64
+    """The field checker ``_field`` and the composition ``_compose64`` of tests/sugar_cases.py in float64
     against get_field_values + get_beta in float64, on the same float32 inputs.  Outputs of all three runs; for run
     "l" (density and the learnable beta) also the gradients to x, points, inv_sr and strengths by ``_run``.  The
     gradients of run "w" pass through sdf and the weighted beta, for which the project has no differentiable CPU
     restatement (``_compose64`` is forward only): they are pinned on the GPU side only.
     Measured: every output and gradient 0 (bitwise: the checker runs the reference's operations in its order)."""
-    from test_gpu_sugar_field import _compose64, _field, _mask, _run
-
     z = fixture("field")
     mode, df, sdf_on, want_op = FIELD_RUNS[run]
     inp = field_inputs(z, K, run)
@@ -521,13 +458,10 @@ def test_field_restatement(K, run):
 
 @pytest.mark.parametrize("K", [1, 16])
 def test_normal_restatement(K):
-    """The normal checker ``_normal`` of tests/test_gpu_sugar_normal.py in float64, in both of its arrangements,
+    """The normal checker ``_normal`` of tests/sugar_cases.py in float64, in both of its arrangements,
     against the body of ``if use_sdf_better_normal_loss:`` in float64: the per-sample loss and the gradient to the
     normals (run a's float32 opacities, the reference's float32 smallest axes).  Measured: 0 (bitwise) as the
     reference writes the sum, 2.1e-16 in the checker's other arrangement."""
-    from test_gpu_sugar_field import _mask
-    from test_gpu_sugar_normal import _normal
-
     z = fixture("field")
     own = z["gaussian_idx"]
     idx = z["knn_idx"][own][:, :K]

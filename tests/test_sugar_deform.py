@@ -2,52 +2,16 @@
 reference's own DeformationNetwork (tests/golden/reference_deform.npz, made by tests/golden/make_golden_deform.py), the
 tables of HexPlaneBinding, DeformationWeights and the argument checks of the C calls."""
 import ctypes
-import os
 
-import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
 import sugar_deform_reference as ref  # noqa: E402
 from diff_gaussian_rasterization import _C  # noqa: E402
+from sugar_deform_reference import CASES, fixture, fixture_reference, fixture_ups, fixture_weights  # noqa: E402
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 RESOLUTION, MULTIRES = (4, 5, 6, 3), (1, 2)
-CASES = {"dg": (True, True), "dg_noscale": (True, False), "vert": (False, True)}  # normalize_rot, d_scale
-_CACHE = {}
-
-
-def fixture():
-    if "z" not in _CACHE:
-        z = np.load(os.path.join(HERE, "golden", "reference_deform.npz"))
-        _CACHE["z"] = {k: (z[k] if z[k].dtype.kind == "U" else torch.from_numpy(z[k])) for k in z.files}
-    return _CACHE["z"]
-
-
-def fixture_weights(z, d_scale):
-    from sugar_deform import DeformationWeights
-
-    return DeformationWeights.from_state_dict({k: z["w_" + k] for k in z["names"]}, d_scale)
-
-
-def fixture_reference(z, case, tag, weights):
-    """{key of sugar_deform_reference.evaluate: the reference's tensor} for what the fixture stores of the case."""
-    out = {k: z[f"{case}_{n}_{tag}"] for k, n in zip(ref.OUTPUTS, ("xyz", "rotation", "scale"))
-           if f"{case}_{n}_{tag}" in z}
-    L6 = len(weights.planes)
-    for i, name in enumerate(weights.names):
-        key = f"{case}_d_{name}_{tag}"
-        if key in z:
-            out[f"dplane{i}" if i < L6 else f"dmlp{i - L6}"] = z[key]
-    return out
-
-
-def fixture_ups(z, d_scale):
-    ups = {"xyz": z["up_xyz"], "rot": z["up_rotation"]}
-    if d_scale:
-        ups["scale"] = z["up_scale"]
-    return ups
 
 
 def _rel(a, b):

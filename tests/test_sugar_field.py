@@ -6,6 +6,7 @@ import ctypes
 import pytest
 
 from diff_gaussian_rasterization import _C
+from kernel_budget import assert_kernel_budget, needs_hipcc
 
 
 def test_library_has_the_entry_points_at_abi_9():
@@ -130,15 +131,8 @@ def test_get_field_values_argument_errors():
         get_field_values(a["x"], a["centers"])  # everything but x is keyword-only
 
 
+@needs_hipcc
 def test_field_kernels_do_not_spill(tmp_path):
-    import os
-    import shutil
-
-    from test_kernel_resources import HIPCC, kernel_resources
-
-    if not (os.path.exists(HIPCC) or shutil.which("hipcc")):
-        pytest.skip("hipcc not in this image")
-    res = {k: v for k, v in kernel_resources("gsr_field.hip", tmp_path).items() if "k_field" in k}
-    assert sum("k_field_sample" in k for k in res) == 2 and sum("k_field_gauss" in k for k in res) == 2, sorted(res)
-    for name, r in res.items():
-        assert r.get("VGPRs Spill", 0) == 0 and r.get("SGPRs Spill", 0) == 0, (name, r)
+    kernels = ("k_field_packE", "k_field_sampleILb0E", "k_field_sampleILb1E", "k_field_gaussILi64E",
+               "k_field_gaussILi16E")
+    assert_kernel_budget("gsr_field.hip", tmp_path, "k_field", dict.fromkeys(kernels, 0), sgpr_too=True)

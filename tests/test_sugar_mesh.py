@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from diff_gaussian_rasterization import _C
+from kernel_budget import assert_kernel_budget, needs_hipcc
 
 torch = pytest.importorskip("torch")
 
@@ -266,16 +267,9 @@ def test_restatement_gradient_does_not_depend_on_the_candidate_row():
         assert float((aligned[k] - first[k]).abs().max()) <= 1e-9 * max(scale, 1.0), k
 
 
+@needs_hipcc
 def test_mesh_kernels_do_not_spill(tmp_path):
-    import os
-    import shutil
-
-    from test_kernel_resources import HIPCC, kernel_resources
-
-    if not (os.path.exists(HIPCC) or shutil.which("hipcc")):
-        pytest.skip("hipcc not in this image")
-    res = {k: v for k, v in kernel_resources("gsr_mesh.hip", tmp_path).items() if "k_mesh" in k}
-    assert len(res) == 3, sorted(res)
+    kernels = ("k_mesh_forwardE", "k_mesh_faceE", "k_mesh_vertexE")
+    res = assert_kernel_budget("gsr_mesh.hip", tmp_path, "k_mesh", dict.fromkeys(kernels, 0), sgpr_too=True)
     for name, r in res.items():
-        assert r.get("VGPRs Spill", 0) == 0 and r.get("SGPRs Spill", 0) == 0, (name, r)
         assert r.get("ScratchSize [bytes/lane]", 0) == 0, (name, r)

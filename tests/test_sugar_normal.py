@@ -7,6 +7,7 @@ import ctypes
 import pytest
 
 from diff_gaussian_rasterization import _C
+from kernel_budget import assert_kernel_budget, needs_hipcc
 
 NAMES = ("gsr_sugar_normal_workspace_bytes", "gsr_sugar_normal_forward", "gsr_sugar_normal_backward")
 
@@ -267,15 +268,8 @@ def test_coarse_density_regulation_needs_a_gpu():
         coarse_density_regulation(*args, 16, True)  # the options are keyword-only
 
 
+@needs_hipcc
 def test_normal_kernels_do_not_spill(tmp_path):
-    import os
-    import shutil
-
-    from test_kernel_resources import HIPCC, kernel_resources
-
-    if not (os.path.exists(HIPCC) or shutil.which("hipcc")):
-        pytest.skip("hipcc not in this image")
-    res = {k: v for k, v in kernel_resources("gsr_normal.hip", tmp_path).items() if "k_normal" in k}
-    assert sum("k_normal_sample" in k for k in res) == 2 and sum("k_normal_gauss" in k for k in res) == 2, sorted(res)
-    for name, r in res.items():
-        assert r.get("VGPRs Spill", 0) == 0 and r.get("SGPRs Spill", 0) == 0, (name, r)
+    kernels = ("k_normal_packE", "k_normal_sampleILb0E", "k_normal_sampleILb1E", "k_normal_gaussILi64E",
+               "k_normal_gaussILi16E")
+    assert_kernel_budget("gsr_normal.hip", tmp_path, "k_normal", dict.fromkeys(kernels, 0), sgpr_too=True)

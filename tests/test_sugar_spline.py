@@ -5,7 +5,7 @@ tests/sugar_spline_reference.py (the checker of the GPU tests) against the fixtu
 entries (which precede any device work).  The kernels' numerics are checked on the GPU in
 tests/test_gpu_sugar_spline.py.
 
-Bars of the fixture comparison, those of tests/test_reference_pins.py for the dynamic stage: max |restatement -
+Bars of the fixture comparison, those of tests/sugar_cases.py for every pinned stage: max |restatement -
 fixture| <= 1e-12 max |fixture| on outputs, 1e-10 on gradients, in float64."""
 import ctypes
 
@@ -17,19 +17,13 @@ from diff_gaussian_rasterization import _C
 torch = pytest.importorskip("torch")
 
 import sugar_spline_reference as ref  # noqa: E402
-from sugar_cases import random_quats  # noqa: E402
+from sugar_cases import GRAD_BAR, OUT_BAR, close, fixture, null_is_usable, random_quats  # noqa: E402
 from sugar_spline import SplineGrid, spline_attributes  # noqa: E402
-from test_reference_pins import GRAD_BAR, OUT_BAR, close, fixture, null_is_usable  # noqa: E402
+from sugar_spline_reference import SPLINE_KEYS, fixture_grid  # noqa: E402
 
 NAMES = ("gsr_sugar_spline_workspace_bytes", "gsr_sugar_spline_forward", "gsr_sugar_spline_backward")
-SPLINE_KEYS = ("xyz", "rotation", "scale", "dknots_xyz", "dknots_rot", "dknots_scale")
 D = torch.float64
 IDENTITY = [0.0, 0.0, 0.0, 1.0]
-
-
-def fixture_grid(z, degree):
-    g = z[f"deg{degree}_grid"]
-    return SplineGrid(degree, g[1].item(), g[0].item(), int(z["knots_xyz"].shape[0]))
 
 
 def restated(dtype, z, degree, scale=True):
