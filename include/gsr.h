@@ -86,7 +86,10 @@ const char* gsr_version(void);
  *      positional; the *_workspace_bytes sizers are unchanged.
  *      Added under 9 (additive: no existing call changes, binders find the new calls by symbol):
  *      gsr_sugar_deform_workspace_bytes / gsr_sugar_deform_forward / gsr_sugar_deform_backward (dynamic SuGaR: the
- *      HexPlane deformation network that produces the control knots).
+ *      HexPlane deformation network that produces the control knots);
+ *      gsr_sugar_meshreg_workspace_bytes / gsr_sugar_normal_consistency_forward / _backward /
+ *      gsr_sugar_laplacian_forward / _backward (SuGaR: the normal-consistency and uniform-Laplacian regularisers of the
+ *      deformed surface mesh, for all frames of a batch).
  */
 #define GSR_ABI_VERSION 9
 int gsr_abi_version(void);
@@ -890,6 +893,69 @@ int gsr_sugar_deform_backward(const gsr_sugar_deform* in, const int* sp_order, c
                               const float* dL_dxyz, const float* dL_drot, const float* dL_dscale,
                               float* const* dL_dplanes, float* const* dL_dmlp, void* workspace, size_t workspace_bytes,
                               void* stream);
+
+/*
+ * gsr_sugar_normal_consistency_* and gsr_sugar_laplacian_*: the two mesh regularisers the SuGaR systems put on the
+ * deformed surface every step, pytorch3d.loss.mesh_normal_consistency(meshes) and mesh_laplacian_smoothing(meshes,
+ * "uniform") (system/sugar_static.py:286-297, system/sugar_4dgen.py:234-250; pytorch3d is [EXT]: stated from its
+ * published algorithm), for T frames of one fixed topology.  V vertices, E unique undirected edges, P face pairs;
+ * T V < 2^31, 4 P < 2^31, T ceil(max(P, V) / 256) < 2^31.  The inputs are the fields of gsr_sugar_meshreg below
+ * (sugar_meshreg.MeshTopology builds the tables once per mesh).
+ * Normal consistency.  pairs (P,4) = (a, b, c0, c1): an edge (a, b), a < b, and the third vertices of two faces on
+ * it (every unordered pair of faces incident to an edge is one row).  With e = x_b - x_a at frame t:
+ *   n0 = e x (x_c0 - x_a);  n1 = -(e x (x_c1 - x_a));  cos = (n0 . n1) / (max(|n0|, 1e-8) max(|n1|, 1e-8))
+ *   nc[t] = (1 / P) sum_p (1 - cos_p)                                                               nc (T,)
+ * (torch's cosine_similarity: each norm clamped on its own.  torch clamps the norm's value in place, outside autograd,
+ * so the backward differentiates cos as written with m = max(|n|, 1e-8) held as |n|'s function: d cos / d n0 =
+ * n1 / (m0 m1) - cos n0 / (m0 |n0|), the second term 0 at n0 = 0, whether the clamp holds or not.)  A row with an entry outside [0, V) adds nothing (P still divides) and nothing of it is
+ * dereferenced.
+ * Backward, given dL_dnc (T,) = g: kernel 1 writes per (t, pair) the four fp64 gradient rows of its corners a, b, c0,
+ * c1, scaled by g_t / P, into the workspace; kernel 2 adds, per (t, vertex i), the rows slots[slot_offsets[i] ..
+ * slot_offsets[i+1]) name (entry 4 pair + role, role 0..3 = a, b, c0, c1) and rounds once: dL_dvert_xyz (T,V,3),
+ * written in full.  A slot entry outside [0, 4 P) is skipped.
+ * Uniform Laplacian.  The one-rings in CSR: vertex i owns ring[ring_offsets[i] .. ring_offsets[i+1]), its distinct
+ * neighbours j (2 E entries in all); deg_i is the row's length.
+ *   d_i = (1 / deg_i) sum_{j in row i} x_j - x_i   (deg_i = 0: d_i = -x_i, pytorch3d subtracts the identity for every
+ *   vertex);   lap[t] = (1 / V) sum_i |d_i|                                                         lap (T,)
+ * Backward, given dL_dlap (T,) = g: kernel 1 writes u_i = g_t d_i / (V |d_i|) (0 at |d_i| = 0, torch's norm) as fp64
+ * rows; kernel 2 writes dL_dvert_xyz[t,i] = -u_i + sum_{j in row i} u_j / deg_j, the exact derivative when the rows
+ * are symmetric (j in row i iff i in row j), as one-rings are.  A ring entry outside [0, V) is skipped.
+ * Both: offsets are clamped to the table's length, a row whose end precedes its start is empty.  A vertex nothing
+ * reaches gets exactly +0.0, and so does every vertex of a frame with g_t = 0 (its work is skipped).
+ * Sum orders (no atomics; two calls give the same bits): a row of at most 32 entries is added in ascending entry
+ * order, from 0; of a longer row, lane l of a 64-lane wave adds the entries l, l + 64, ... in order, from 0, and the 64
+ * partial sums are added pairwise by a butterfly (lanes 32 apart first, then 16, ... 1).  The forwards: each block of
+ * 256 consecutive pairs (vertices) of a frame adds its lanes' terms by that butterfly per wave and the four wave sums
+ * in ascending order; one wave per frame adds the block sums the same way (lane l: l, l + 64, ...; butterfly) and
+ * divides by P (V).
+ * Precision: fp64 arithmetic from the fp32 inputs; nc, lap and the gradients are rounded to fp32 once.
+ * workspace: gsr_sugar_meshreg_workspace_bytes(T, V, P, pass) bytes of device memory (256-B aligned; 0 for an unknown
+ * pass): GSR_MESHREG_FORWARD (either forward): 8 T ceil(max(P, V, 1) / 256) bytes of fp64 block sums;
+ * GSR_MESHREG_NC_BACKWARD: 96 T P bytes, GSR_MESHREG_LAP_BACKWARD: 24 T V bytes of fp64 rows.  Every call is two launches on `stream`; the library allocates nothing.  T = 0 launches
+ * nothing; so does P = 0 for the normal consistency and V = 0 for the Laplacian (the caller's nc / lap / gradients
+ * are then zero: nothing is written).
+ */
+#define GSR_MESHREG_FORWARD 0
+#define GSR_MESHREG_NC_BACKWARD 1
+#define GSR_MESHREG_LAP_BACKWARD 2
+typedef struct gsr_sugar_meshreg {
+  int T, V, E, P;          /* frames, vertices, unique undirected edges, face pairs */
+  const float* vert_xyz;   /* (T,V,3): the deformed vertices */
+  const int* pairs;        /* (P,4) int32 (a, b, c0, c1); 16-byte aligned */
+  const int* slot_offsets; /* (V+1,) int32 */
+  const int* slots;        /* (4P,) int32: 4 pair + role, ascending within a row */
+  const int* ring_offsets; /* (V+1,) int32 */
+  const int* ring;         /* (2E,) int32: the neighbour j, ascending within a row */
+} gsr_sugar_meshreg;
+size_t gsr_sugar_meshreg_workspace_bytes(int T, int V, int P, int pass);
+int gsr_sugar_normal_consistency_forward(const gsr_sugar_meshreg* in, float* nc, void* workspace,
+                                         size_t workspace_bytes, void* stream);
+int gsr_sugar_normal_consistency_backward(const gsr_sugar_meshreg* in, const float* dL_dnc, float* dL_dvert_xyz,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+int gsr_sugar_laplacian_forward(const gsr_sugar_meshreg* in, float* lap, void* workspace, size_t workspace_bytes,
+                                void* stream);
+int gsr_sugar_laplacian_backward(const gsr_sugar_meshreg* in, const float* dL_dlap, float* dL_dvert_xyz,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * The view-segmented stable LSD radix sort that every sort of this library runs (the depth sort, the tile sort and

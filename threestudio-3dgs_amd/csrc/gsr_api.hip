@@ -909,6 +909,86 @@ int gsr_sugar_deform_backward(const gsr_sugar_deform* in, const int* sp_order, c
   return last_launch();
 }
 
+// ---- the mesh regularisers of the deformed surface (gsr_meshreg.hip) --------------------------------
+static int meshreg_check(const gsr_sugar_meshreg& c) {
+  if (c.T < 0 || c.V < 0 || c.E < 0 || c.P < 0) return fail(GSR_EINVAL, "%s", "negative size");
+  const long long most = c.P > c.V ? c.P : c.V;
+  if (!below_2_31(c.T, c.V) || !below_2_31(4, c.P) || !below_2_31(2, c.E) || !below_2_31(c.T, (most + 255) / 256))
+    return fail(GSR_EINVAL, "%s", "T x V, 4 P, 2 E and T x ceil(max(P, V) / 256) must stay below 2^31");
+  return GSR_OK;
+}
+static int null_named(const char* name) { return fail(GSR_EINVAL, "null pointer argument: %s", name); }
+// the arguments of one loss (nc: the normal consistency), `out` being the tensor it writes
+static int meshreg_args(const gsr_sugar_meshreg& c, bool nc, const void* out, const char* out_name,
+                        const void* workspace, size_t workspace_bytes, bool backward) {
+  const int pass = !backward ? GSR_MESHREG_FORWARD : nc ? GSR_MESHREG_NC_BACKWARD : GSR_MESHREG_LAP_BACKWARD;
+  if (c.vert_xyz == nullptr) return null_named("vert_xyz");
+  if (nc) {
+    if (c.pairs == nullptr) return null_named("pairs");
+    if (backward && c.slot_offsets == nullptr) return null_named("slot_offsets");
+    if (backward && c.slots == nullptr) return null_named("slots");
+  } else {
+    if (c.ring_offsets == nullptr) return null_named("ring_offsets");
+    if (c.E > 0 && c.ring == nullptr) return null_named("ring");
+  }
+  if (out == nullptr) return null_named(out_name);
+  if (workspace == nullptr) return null_named("workspace");
+  if (((uintptr_t)c.pairs & 15u) != 0) return fail(GSR_EINVAL, "%s", "pairs must be 16-byte aligned");
+  if (((uintptr_t)workspace & 7u) != 0) return fail(GSR_EINVAL, "%s", "workspace must be 8-byte aligned");
+  if (workspace_bytes < meshreg_workspace_bytes(c.T, c.V, c.P, pass))
+    return fail(GSR_EINVAL, "%s", "workspace too small");
+  return GSR_OK;
+}
+
+size_t gsr_sugar_meshreg_workspace_bytes(int T, int V, int P, int pass) {
+  if (pass < GSR_MESHREG_FORWARD || pass > GSR_MESHREG_LAP_BACKWARD) return 0;
+  return meshreg_workspace_bytes(T < 0 ? 0 : T, V < 0 ? 0 : V, P < 0 ? 0 : P, pass);
+}
+
+int gsr_sugar_normal_consistency_forward(const gsr_sugar_meshreg* in, float* nc, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  if (in == nullptr) return null_argument();
+  if (meshreg_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->T == 0 || in->P == 0) return nothing_to_do();
+  if (meshreg_args(*in, true, nc, "nc", workspace, workspace_bytes, false) != GSR_OK) return GSR_EINVAL;
+  launch_normal_consistency_forward(*in, nc, workspace, (hipStream_t)stream);
+  return last_launch();
+}
+
+int gsr_sugar_normal_consistency_backward(const gsr_sugar_meshreg* in, const float* dL_dnc, float* dL_dvert_xyz,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+  if (in == nullptr) return null_argument();
+  if (meshreg_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->T == 0 || in->P == 0) return nothing_to_do();
+  if (dL_dnc == nullptr) return null_named("dL_dnc");
+  if (meshreg_args(*in, true, dL_dvert_xyz, "dL_dvert_xyz", workspace, workspace_bytes, true) != GSR_OK)
+    return GSR_EINVAL;
+  launch_normal_consistency_backward(*in, dL_dnc, dL_dvert_xyz, workspace, (hipStream_t)stream);
+  return last_launch();
+}
+
+int gsr_sugar_laplacian_forward(const gsr_sugar_meshreg* in, float* lap, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+  if (in == nullptr) return null_argument();
+  if (meshreg_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->T == 0 || in->V == 0) return nothing_to_do();
+  if (meshreg_args(*in, false, lap, "lap", workspace, workspace_bytes, false) != GSR_OK) return GSR_EINVAL;
+  launch_laplacian_forward(*in, lap, workspace, (hipStream_t)stream);
+  return last_launch();
+}
+
+int gsr_sugar_laplacian_backward(const gsr_sugar_meshreg* in, const float* dL_dlap, float* dL_dvert_xyz,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  if (in == nullptr) return null_argument();
+  if (meshreg_check(*in) != GSR_OK) return GSR_EINVAL;
+  if (in->T == 0 || in->V == 0) return nothing_to_do();
+  if (dL_dlap == nullptr) return null_named("dL_dlap");
+  if (meshreg_args(*in, false, dL_dvert_xyz, "dL_dvert_xyz", workspace, workspace_bytes, true) != GSR_OK)
+    return GSR_EINVAL;
+  launch_laplacian_backward(*in, dL_dlap, dL_dvert_xyz, workspace, (hipStream_t)stream);
+  return last_launch();
+}
+
 // ---- the view-segmented radix sort (tests: every sort of the library runs seg_sort) -----------------
 struct SortWork {
   uint32_t *keys2, *vals2, *counts, *totals;

@@ -333,6 +333,18 @@ void launch_deform_forward(const DeformCall& c, float* xyz, float* rot, float* s
 void launch_deform_backward(const DeformCall& c, const DeformCsr& t, const float* g_xyz, const float* g_rot,
                             const float* g_scale, float* const* dplanes, float* const* dmlp, void* workspace,
                             hipStream_t stream);
+// The normal-consistency and uniform-Laplacian regularisers of the deformed mesh (include/gsr.h
+// gsr_sugar_normal_consistency_* / gsr_sugar_laplacian_*) — gsr_meshreg.hip.  T frames, V vertices, P face pairs, the
+// vertex -> pair-slot table and the one-rings in CSR.  The forwards' workspace holds one fp64 partial sum per block,
+// the backwards' the fp64 rows between their two kernels.
+using MeshRegCall = gsr_sugar_meshreg;
+size_t meshreg_workspace_bytes(int T, int V, int P, int pass);
+void launch_normal_consistency_forward(const MeshRegCall& c, float* nc, void* workspace, hipStream_t stream);
+void launch_normal_consistency_backward(const MeshRegCall& c, const float* g_nc, float* dxyz, void* workspace,
+                                        hipStream_t stream);
+void launch_laplacian_forward(const MeshRegCall& c, float* lap, void* workspace, hipStream_t stream);
+void launch_laplacian_backward(const MeshRegCall& c, const float* g_lap, float* dxyz, void* workspace,
+                               hipStream_t stream);
 void launch_gauss_backward(const GaussBackwardArgs& a, ViewGradArgs va, const AccumArgs& b, hipStream_t stream);
 
 }  // namespace gsr

@@ -101,10 +101,15 @@ class SugarDeform(ctypes.Structure):
                 + _fields(_vpp, "planes mlp") + _fields(_vp, "cell frac tcell tfrac"))
 
 
+class SugarMeshReg(ctypes.Structure):
+    _fields_ = _fields(_i, "T V E P") + _fields(_vp, "vert_xyz pairs slot_offsets slots ring_offsets ring")
+
+
 STRUCTS = {"gsr_set_scene": SetScene, "gsr_set_state": SetState, "gsr_set_outputs": SetOutputs,
            "gsr_set_grads": SetGrads, "gsr_sugar_field": SugarField, "gsr_sugar_normal": SugarNormal,
            "gsr_sugar_mesh": SugarMesh, "gsr_sugar_skin": SugarSkin, "gsr_sugar_timed": SugarTimed,
-           "gsr_sugar_arap": SugarArap, "gsr_sugar_spline": SugarSpline, "gsr_sugar_deform": SugarDeform}
+           "gsr_sugar_arap": SugarArap, "gsr_sugar_spline": SugarSpline, "gsr_sugar_deform": SugarDeform,
+           "gsr_sugar_meshreg": SugarMeshReg}
 
 # name -> (restype, argtypes); must match include/gsr.h exactly (checked by tests/test_abi.py)
 SIGNATURES = {
@@ -170,6 +175,11 @@ SIGNATURES = {
     "gsr_sugar_deform_forward": (_i, [_P(SugarDeform)] + [_vp] * 3 + [_vp]),
     # (the six tables, three upstream gradients, the host arrays of plane and MLP gradient pointers, workspace)
     "gsr_sugar_deform_backward": (_i, [_P(SugarDeform)] + [_vp] * 6 + [_vp] * 3 + [_vpp] * 2 + [_vp, _sz, _vp]),
+    "gsr_sugar_meshreg_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gsr_sugar_normal_consistency_forward": (_i, [_P(SugarMeshReg)] + [_vp] + [_vp, _sz, _vp]),
+    "gsr_sugar_normal_consistency_backward": (_i, [_P(SugarMeshReg)] + [_vp] + [_vp] + [_vp, _sz, _vp]),
+    "gsr_sugar_laplacian_forward": (_i, [_P(SugarMeshReg)] + [_vp] + [_vp, _sz, _vp]),
+    "gsr_sugar_laplacian_backward": (_i, [_P(SugarMeshReg)] + [_vp] + [_vp] + [_vp, _sz, _vp]),
     "gsr_set_geom_bytes": (_sz, [_i, _i]),
     "gsr_set_binning_bytes": (_sz, [_i, _i, ctypes.POINTER(_i), _i, _i]),
     "gsr_set_image_bytes": (_sz, [_i, _i, _ip, _i, _i, _i]),
