@@ -466,5 +466,44 @@ def gpu_sort_pairs(keys, vals, sizes, key_bits, max_bits):
     return k.cpu().numpy().view(np.uint32), (v.cpu().numpy().view(np.uint32) if v is not None else None)
 
 
+SORT_GUARD_BYTES = 4096
+SORT_GUARD_BYTE = 0xA5
+
+
+def gpu_sort_pairs_guarded(keys, vals, sizes, key_bits, max_bits):
+    """gpu_sort_pairs with SORT_GUARD_BYTES of SORT_GUARD_BYTE behind the keys, the values and the work buffer, all
+    three stated to the library at their plain sizes (sum(sizes) items, gsr_sort_work_bytes): (sorted keys, sorted
+    values, names of the arrays whose tail the sort wrote to).  The tails are the test's own memory."""
+    import torch
+
+    from diff_gaussian_rasterization import _C
+
+    lib = _C.load_library()
+    n = (ctypes.c_int * len(sizes))(*sizes)
+    total = int(sum(sizes))
+    assert total == keys.size and (vals is None or vals.size == total)
+    wb = lib.gsr_sort_work_bytes(len(sizes), n)
+    assert wb > 0
+
+    def guarded(nbytes, payload):
+        buf = torch.full((nbytes + SORT_GUARD_BYTES,), SORT_GUARD_BYTE, dtype=torch.uint8, device="cuda")
+        if payload is not None:
+            buf[:nbytes].copy_(torch.from_numpy(payload.view(np.uint8)))
+        return buf
+
+    bufs = {"keys": guarded(4 * total, keys), "work": guarded(wb, None)}
+    if vals is not None:
+        bufs["vals"] = guarded(4 * total, vals)
+    rc = lib.gsr_sort_pairs(len(sizes), n, ctypes.c_void_p(bufs["keys"].data_ptr()),
+                            ctypes.c_void_p(bufs["vals"].data_ptr()) if vals is not None else None, key_bits, max_bits,
+                            ctypes.c_void_p(bufs["work"].data_ptr()), wb,
+                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0, lib.gsr_last_error()
+    torch.cuda.synchronize()
+    touched = [name for name, b in bufs.items() if bool((b[-SORT_GUARD_BYTES:] != SORT_GUARD_BYTE).any())]
+    out = {name: bufs[name][:4 * total].cpu().numpy().view(np.uint32) for name in bufs if name != "work"}
+    return out["keys"], out.get("vals"), touched
+
+
 __all__ = ["gs", "make_camera", "oracle_cam", "gpu_render", "run_oracle", "check_forward", "check_grads",
            "check_radii", "adjudicate", "print_report", "last_num_rendered", "flip_excuse", "flip_dependents"]
