@@ -13,6 +13,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import shading_cases as cases  # noqa: E402
 import torch_reference as tr  # noqa: E402
 
 
@@ -55,6 +56,19 @@ def _check(name, got, ref64, ref32, tol):
     assert err <= bar, f"{name}: max err {err:.3g} > {bar:.3g} (torch fp32 yardstick {yard:.3g})"
 
 
+def _check_pixels(tag, scenes, got, **kw):
+    """The per-pixel bar of tests/shading_cases.py (the tighter one) on the same scenes: `got` is one dict per view
+    by the names of shading_cases.reference; keywords given as lists are per view."""
+    f32 = cases.as_float32(scenes)
+    ties = None
+    if kw.get("entry", "shade") == "shade":
+        ties, _ = cases.tie_masks(f32, kw["shading"], kw.get("use_pred", False), kw["ka"], kw["kd"])
+    for v, s in enumerate(f32):
+        one = {k: (x[v] if isinstance(x, list) else x) for k, x in kw.items()}
+        r64, n32 = cases.references(s, **one)
+        cases.check_pixels(got[v], r64, n32, None if ties is None else ties[v], tag=f"{tag} view {v}")
+
+
 def _reference(sc, dtype, shading, use_pred, ka, kd):
     leaves = {k: sc[k].to(dtype).clone().requires_grad_(True) for k in ("color", "depth", "alpha", "bg")}
     outs = tr.shading_epilogue(leaves["color"], leaves["depth"], leaves["alpha"], sc["rays_o"].to(dtype),
@@ -92,6 +106,9 @@ def test_shade_views_match_torch(shading, use_pred, V, H, W):
             _check(f"view {v} {name}", got, r64, r32, 1e-5)
         for k in ("color", "depth", "alpha", "bg"):
             _check(f"view {v} d{k}", leaves[k].grad[v], g64[k], g32[k], 1e-4)
+    got = [dict(render=render[v], normal=nmap[v], depth=depth[v], **{"d" + k: leaves[k].grad[v] for k in leaves})
+           for v in range(V)]
+    _check_pixels(f"match_torch {shading} {H}x{W}", scenes, got, shading=shading, use_pred=use_pred, ka=ka, kd=kd)
 
 
 @pytest.mark.gpu
@@ -119,6 +136,9 @@ def test_shade_views_per_view_lights_and_modes(V, H, W):
             _check(f"view {v} {name}", got, r64, r32, 1e-5)
         for k in ("color", "depth", "alpha", "bg"):
             _check(f"view {v} d{k}", leaves[k].grad[v], g64[k], g32[k], 1e-4)
+    got = [dict(render=render[v], normal=nmap[v], depth=depth[v], **{"d" + k: leaves[k].grad[v] for k in leaves})
+           for v in range(V)]
+    _check_pixels(f"per_view_tables V={V}", scenes, got, shading=modes, ka=ka, kd=kd)
 
 
 def test_shade_tables_host_checks():
@@ -189,6 +209,8 @@ def test_depth_normal_views_match_torch(V, H, W):
         _check("nmap", nmap[v], o64[1], o32[1], 1e-5)
         _check("ddepth", depth.grad[v], d64, d32, 1e-4)
         _check("dalpha", alpha.grad[v], a64, a32, 1e-4)
+    got = [dict(unit=unit[v], nmap=nmap[v], ddepth=depth.grad[v], dalpha=alpha.grad[v]) for v in range(V)]
+    _check_pixels(f"depth_normal {H}x{W}", scenes, got, entry="depth_normal")
 
 
 def test_shading_has_no_cpu_path():

@@ -68,8 +68,12 @@ __device__ __forceinline__ float bg_at(const ShadeArgs& A, int v, size_t HW, siz
   return A.bg_layout == 0 ? A.bg[3 * v + c] : A.bg[((size_t)v * HW + p) * 3 + c];
 }
 
-// X = rays_o + depth * rays_d at image position (x, y) of view v, 0 outside the image (zero padding)
+// X = rays_o + depth * rays_d at image position (x, y) of view v, 0 outside the image (zero padding).
+// Rounded as torch rounds it (the product, then the sum): the kernels' contract(off) does not reach into this
+// helper, and a fused multiply-add here changes the last bit of X, which the central differences at a silhouette
+// (|a| ~ 1e-2 from |X| ~ 1) magnify past what the float32 restatement itself misses.
 __device__ __forceinline__ P3 load_X(const ShadeArgs& A, int v, int x, int y) {
+#pragma clang fp contract(off)
   if (x < 0 || y < 0 || x >= A.W || y >= A.H) return p3(0.f, 0.f, 0.f);
   const size_t HW = (size_t)A.H * A.W, p = (size_t)y * A.W + x;
   const float z = A.depth[(size_t)v * HW + p];
@@ -243,9 +247,16 @@ __device__ __forceinline__ void shade_bwd_pixel(const ShadeArgs& A, const ShadeG
     if (own_normal) gu = p3(gu.x + ddt * l.x, gu.y + ddt * l.y, gu.z + ddt * l.z);
     const P3 dlv = normalize_bwd(L, llen, p3(ddt * s.x, ddt * s.y, ddt * s.z));
     dXl = p3(-dlv.x, -dlv.y, -dlv.z);
-  } else if (own && G.d_color != nullptr) {
+  } else if (own) {
+    // no upstream gradient of the render (NULL = zero): the colour and background gradients are written as zeros
+    if (G.d_color != nullptr) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) G.d_color[plane + k * HW] = 0.0f;
+      for (int k = 0; k < 3; ++k) G.d_color[plane + k * HW] = 0.0f;
+    }
+    if (G.d_bg != nullptr && A.bg_layout != 0) {
+      float* o = G.d_bg + ((size_t)v * HW + p) * 3;
+      o[0] = o[1] = o[2] = 0.0f;
+    }
   }
   // u = n / den, n = -(a x b): dL/da = gn' x b... with gc = -gn: Ga = b x gc = gn x b, Gb = gc x a = a x gn
   const P3 gn = normalize_bwd(n, len, gu);
