@@ -89,7 +89,9 @@ const char* gsr_version(void);
  *      HexPlane deformation network that produces the control knots);
  *      gsr_sugar_meshreg_workspace_bytes / gsr_sugar_normal_consistency_forward / _backward /
  *      gsr_sugar_laplacian_forward / _backward (SuGaR: the normal-consistency and uniform-Laplacian regularisers of the
- *      deformed surface mesh, for all frames of a batch).
+ *      deformed surface mesh, for all frames of a batch);
+ *      gsr_set_timed / gsr_set_timed_grads and gsr_set_timed_preprocess / gsr_set_timed_backward (timed view sets: every
+ *      view of a set renders its own frame of the Gaussians' geometry, e.g. the frames of dynamic SuGaR).
  */
 #define GSR_ABI_VERSION 9
 int gsr_abi_version(void);
@@ -316,6 +318,47 @@ int gsr_set_render(const gsr_set_scene* scene, const gsr_set_state* state, const
 int gsr_set_backward(const gsr_set_scene* scene, const gsr_set_state* state, const gsr_set_grads* grads,
                      void* stream);
 int gsr_grad_chunk_range(int P, int n_chunks, int chunk, int* g0, int* g1);
+
+/*
+ * Timed view sets: a view set whose views each carry their own Gaussian geometry — frame v of a time batch rendered
+ * from camera v (renderer/diff_sugar_rasterizer_temporal.py:150-192 and renderer/diff_gaussian_rasterizer_st.py call
+ * the rasterizer once per frame; gsr_sugar_timed_forward returns all frames at once as (T,N,.) arrays).  Every stage
+ * stays one launch per set.  The state, the size queries, gsr_set_num_rendered and gsr_set_render are those of a plain
+ * set (gsr_set_render reads no geometry array of the scene); only the preprocess and the backward have timed twins.
+ *
+ * gsr_set_timed: per-view arrays, view-major.  A non-NULL field replaces the scene's shared array of that name for
+ * this set (the scene's field is then ignored and may be NULL); a NULL field means "shared, as in a plain set".
+ * means3D_v (V,P,3) is required; scales_v (V,P,3), rotations_v (V,P,4) and colors2_v (V,P,3) are optional.  With
+ * colors2_v the preprocess writes view v's second colour into view v's records and remembers the pointer: pass
+ * colors2_v itself as gsr_set_outputs.colors2 and gsr_set_grads.colors2 and the blends read the records (the pointer
+ * is the key, see gsr_set_outputs.colors2); a shared second colour set (P,3) is not embedded: the blends gather it.
+ * Opacities and colours are shared.  Not built, rejected with GSR_EINVAL before any device work: shs (the timed
+ * renderers pass precomputed colours), cov3D_precomp, and in the backward colors_override and n_chunks > 0.
+ */
+typedef struct gsr_set_timed {
+  const float *means3D_v, *scales_v, *rotations_v, *colors2_v;
+} gsr_set_timed;
+
+/*
+ * The per-view gradients of a timed set: the shapes of the inputs, one row per (view, Gaussian), NOT summed over the
+ * views, and always overwritten (accumulate does not apply): a (view, Gaussian) the view's blend did not reach gets
+ * exactly +0.  dL_dmeans3D_v is required; each of the others is required when its input is per view and ignored when
+ * it is not.  The gradients of what stays shared go through gsr_set_grads as for a plain set, summed over the views
+ * in view order and continued across sets and view groups with `accumulate`: dL_dopacity, dL_dcolors, dL_dscales
+ * (scales_v NULL), dL_drotations (rotations_v NULL), dL_dcolors2 (colors2 shared).  gsr_set_grads.dL_dmeans3D,
+ * dL_dcov3D and dL_dsh are not used and may be NULL (accumulate needs no dL_dcov3D here: the scale and rotation
+ * gradients are formed per view from that view's dL/dcov3D and summed).  Two runs give the same bits.
+ */
+typedef struct gsr_set_timed_grads {
+  float *dL_dmeans3D_v, *dL_dscales_v, *dL_drotations_v, *dL_dcolors2_v;
+} gsr_set_timed_grads;
+
+/* gsr_set_preprocess of a timed set. */
+int gsr_set_timed_preprocess(const gsr_set_scene* scene, const gsr_set_state* state, const gsr_set_timed* timed,
+                             void* stream);
+/* gsr_set_backward of a timed set (after gsr_set_timed_preprocess + gsr_set_render with the same arrays). */
+int gsr_set_timed_backward(const gsr_set_scene* scene, const gsr_set_state* state, const gsr_set_grads* grads,
+                           const gsr_set_timed* timed, const gsr_set_timed_grads* timed_grads, void* stream);
 
 /*
  * Optional phase timing with HIP events recorded on the launch stream around each phase's kernels.

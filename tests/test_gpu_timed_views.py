@@ -1,0 +1,195 @@
+"""Timed view sets on the GPU (rasterize_timed_views, include/gsr.h gsr_set_timed_*): every view renders its own frame
+of the Gaussians' geometry.  Against the oracle per frame, against one one-view rasterize_views call per frame (what
+the project offered before), across set / view-group splits, and through the batch renderer's "sugar_temporal" mode.
+
+Base scene (tests/timed_views_fixtures.make_frames): 4133 Gaussians (past the 4096 the per-(view, Gaussian) kernels
+of the plain path slice by, no multiple of 256), 72x56 images (no multiple of the 16-pixel tile), frames turned, moved
+and rescaled so that frame 0's geometry in view v > 0 is another image, a block of Gaussians behind the camera in the
+odd frames only.  Bars as tests/gsr_testutil.py, unchanged."""
+import numpy as np
+import pytest
+import torch
+
+import renderer_fixtures as rf
+import timed_views_fixtures as tf
+from gsr_testutil import (GRAD_TOL, _sum_grads, _view, check_forward, check_grads, flip_excuse, gs, make_camera,
+                          print_report, run_oracle)
+
+pytestmark = pytest.mark.gpu
+
+P = 4133
+BGS = [[1.0, 1.0, 1.0], [0.0, 0.0, 0.0], [0.2, 0.5, 0.9], [0.7, 0.1, 0.3]]
+PER_VIEW = ("means3D", "scales", "rotations", "means2D")
+
+
+@pytest.fixture(autouse=True)
+def _parity_report():
+    yield
+    print_report()
+
+
+def _cams(V, W=72, H=56):
+    return [make_camera(W, H, elevation=7.0 * (i % 5), azimuth=50.0 * i + 15.0) for i in range(V)]
+
+
+def _ups(V, W=72, H=56, seed=60):
+    return [gs.upstream_grads(H, W, seed=seed + v) for v in range(V)]
+
+
+def _within_bar(got, want, what):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    err = np.abs(got - want) / np.maximum(1.0, np.abs(want))
+    assert float(err.max(initial=0.0)) <= GRAD_TOL, f"{what}: {float(err.max())} at {int(err.argmax())}"
+
+
+@pytest.mark.parametrize("V,W,H,seed", [(3, 72, 56, 34), (9, 48, 40, 32), (1, 72, 56, 33)])
+def test_timed_set_vs_oracle(V, W, H, seed):
+    """Frame v from camera v against the oracle on that frame: images, radii, K, view v's rows of the per-view
+    means3D / scales / rotations gradients and means2D; the shared opacity and colour gradients against the sums over
+    the views.  V = 9 is past the <= 8-view split backward; V = 1 is a set of one.
+    Seeds 34 / 32 / 33: the fp32 oracle misses the fp64 bar on 0 pixels and 0 gradient rows in every view of all three
+    cases (computed on the CPU; keys means3D, scales, rotations, means2D, opacity, colors), so FLIP_RATIO x that count
+    + FLIP_SLACK allows 3 rows in 4133 per tensor — reading another frame's geometry misses thousands.  (Seed 31 was
+    passed over: its view 0 has 25 such pixels and 42 rows of the oracle's own, which would allow 87.)"""
+    cams, ups = _cams(V, W, H), _ups(V, W, H)
+    bgs = [BGS[v % 4] for v in range(V)]
+    frames = tf.make_frames(P, cams, seed)
+    gpu = tf.run_timed(frames, cams, bgs, ups)
+    refs = []
+    for v in range(V):
+        ref = run_oracle(frames[v], cams[v], bgs[v], grads=ups[v])
+        check_forward(_view(gpu, v), ref, f"timed view {v}", K_gpu=gpu["K"][v])
+        check_grads({"g_" + k: gpu["g_" + k][v] for k in PER_VIEW}, ref, list(PER_VIEW), f"timed view {v}")
+        refs.append(ref)
+    keys = ["opacity", "colors"]
+    tot = dict(b32=_sum_grads(refs, "b32", keys), b64=_sum_grads(refs, "b64", keys),
+               b32r=_sum_grads(refs, "b32r", keys))
+    check_grads(gpu, tot, keys, "timed summed", excuse=flip_excuse(refs))
+    # the frames do differ: frame 0's geometry for the last view is not within any bar
+    if V > 1:
+        other = run_oracle(frames[0], cams[V - 1], bgs[V - 1])
+        assert np.abs(other["f64"]["color"] - gpu["color"][V - 1]).max() > 0.05
+
+
+@pytest.mark.parametrize("variant", ["per_view", "shared_scales", "background"])
+def test_timed_set_vs_one_view_calls(variant):
+    """V = 4 with per-view colors2 and the fused clamp against rasterize_views once per frame: images bitwise; per-view
+    gradients (dL/dcolors2 included) and the shared sums within the gradient bar.  shared_scales: scales (P, 3), their
+    gradient the sum over the views.  background: the fused composite and dL/dbg."""
+    V = 4
+    cams, ups = _cams(V), _ups(V, seed=70)
+    ups2 = [gs.upstream_grads(56, 72, seed=90 + v)[0] for v in range(V)]
+    frames = tf.make_frames(P, cams, 41)
+    kw = dict(two=True, ups2=ups2, shared_scales=variant == "shared_scales", clamp=variant != "background")
+    bgs = BGS
+    if variant == "background":
+        kw["background"] = np.random.default_rng(5).random((V, 56, 72, 3)).astype(np.float32)
+        bgs = [[0.0, 0.0, 0.0]] * V
+    got = tf.run_timed(frames, cams, bgs, ups, **kw)
+    want = tf.run_loop(frames, cams, bgs, ups, **kw)
+    for k in ("color", "color2", "depth", "alpha", "radii"):
+        assert np.array_equal(got[k], want[k]), k
+    assert (got["radii"][1, tf.BEHIND] == 0).all() and (got["radii"][0, tf.BEHIND] > 0).any()
+    keys = ["means3D", "rotations", "colors2", "means2D", "scales", "opacity", "colors"]
+    if variant == "background":
+        keys.append("background")
+    for k in keys:
+        _within_bar(got["g_" + k], want["g_" + k], k)
+    assert got["g_scales"].shape == ((P, 3) if variant == "shared_scales" else (V, P, 3))
+
+
+def test_identical_frames_equal_the_shared_set():
+    """All frames equal: the image bits of rasterize_views on the shared scene; the per-view gradients summed over the
+    views within the bar of its summed gradients."""
+    from gsr_testutil import _gpu_views
+
+    V = 3
+    cams, ups = _cams(V), _ups(V, seed=75)
+    frames = tf.make_frames(P, cams, 43, identical=True)
+    got = tf.run_timed(frames, cams, BGS[:V], ups)
+    want = _gpu_views(frames[0], cams, BGS[:V], ups)
+    for k in ("color", "depth", "alpha", "radii"):
+        assert np.array_equal(got[k], want[k]), k
+    for k in ("means3D", "scales", "rotations"):
+        _within_bar(got["g_" + k].astype(np.float64).sum(0), want["g_" + k], k)
+    for k in ("opacity", "colors"):
+        _within_bar(got["g_" + k], want["g_" + k], k)
+    _within_bar(got["g_means2D"], np.stack(want["g_means2D"]), "means2D")
+
+
+@pytest.mark.parametrize("V,knob,value", [(5, "SET_MAX", 2), (6, "WORK_BUDGET", 1)])
+def test_sets_and_view_groups_are_bitwise_invariant(V, knob, value, monkeypatch):
+    """Split into sets of 2 views (SET_MAX) or into one-view backward groups (WORK_BUDGET = 1): every gradient has the
+    bits of the single set / single group."""
+    from diff_gaussian_rasterization import batched
+
+    cams, ups = _cams(V), _ups(V, seed=80)
+    ups2 = [gs.upstream_grads(56, 72, seed=95 + v)[0] for v in range(V)]
+    frames = tf.make_frames(P, cams, 44)
+    bgs = [BGS[v % 4] for v in range(V)]
+    kw = dict(two=True, ups2=ups2, shared_scales=True, clamp=True)
+    one = tf.run_timed(frames, cams, bgs, ups, **kw)
+    monkeypatch.setattr(batched, knob, value)
+    split = tf.run_timed(frames, cams, bgs, ups, **kw)
+    for k in one:
+        if k != "K":
+            assert np.array_equal(one[k], split[k]), k
+
+
+def test_culled_rows_are_exact_zeros_and_backward_repeats():
+    """A (view, Gaussian) culled in that view has exactly zero rows in every per-view gradient; two backward passes
+    of one forward give the same bits."""
+    V = 4
+    cams, ups = _cams(V), _ups(V, seed=85)
+    ups2 = [gs.upstream_grads(56, 72, seed=99 + v)[0] for v in range(V)]
+    frames = tf.make_frames(P, cams, 45)
+    got = tf.run_timed(frames, cams, BGS, ups, two=True, ups2=ups2, clamp=True, twice=True)
+    culled = got["radii"] == 0
+    assert culled[1, tf.BEHIND].all() and not culled[0, tf.BEHIND].all()
+    for k in ("means3D", "scales", "rotations", "colors2", "means2D"):
+        rows = got["g_" + k][culled]
+        assert rows.size and not rows.any() and not np.signbit(rows).any(), k
+        assert np.abs(got["g_" + k][~culled]).max() > 0, k
+    for k in [k for k in got if k.startswith("g_")]:
+        assert np.array_equal(got[k], got["h_" + k[2:]]), k
+
+
+def _close(a, b, tol, what):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    err = (a - b).abs() / b.abs().clamp(min=1.0)
+    assert float(err.max()) <= tol, f"{what}: {float(err.max())} (at {int(err.argmax())})"
+
+
+def test_sugar_temporal_mode_matches_per_view_loop():
+    """The batch renderer's "sugar_temporal" mode on the HIP path (B = 4, make_sugar_scene(2) deformed per frame)
+    against the same renderer with batch_render_mode = "per_view", compared as
+    test_gpu_batch_renderer.test_fused_mode_matches_per_view_loop compares the SuGaR modes."""
+    B, H, W = 4, rf.H, rf.W
+    scene = gs.make_sugar_scene(2, sh_degree=0, seed=2)
+    scene["shs"] = scene["shs"][:, :1]
+    batch = tf.make_timed_batch(B, H, W, "cuda", seed=3)
+    fused = tf.TimedRenderer("sugar_temporal", scene, "cuda")
+    ref = tf.TimedRenderer("per_view", scene, "cuda")
+    out_f = fused.batch_forward(dict(batch))
+    out_r = ref.batch_forward(dict(batch))
+    assert fused.geometry.calls == dict(attributes=1, normals=1)
+    keys = sorted(k for k in out_r if k.startswith("comp_"))
+    assert keys == sorted(k for k in out_f if k.startswith("comp_")), (keys, list(out_f))
+    for k in keys:
+        assert out_f[k].shape == out_r[k].shape, k
+        _close(out_f[k], out_r[k], 1e-5, k)
+    for v in range(B):
+        assert torch.equal(out_f["radii"][v], out_r["radii"][v])
+        assert torch.equal(out_f["visibility_filter"][v], out_r["visibility_filter"][v])
+    rf.loss_of(out_f).backward()
+    rf.loss_of(out_r).backward()
+    tol = 1e-2  # (the depth -> normal stencil, see test_fused_mode_matches_per_view_loop)
+    for v in range(B):
+        _close(out_f["viewspace_points"][v].grad, out_r["viewspace_points"][v].grad, tol, f"viewspace {v}")
+    for k, p in fused.geometry.params.items():
+        q = ref.geometry.params[k]
+        if q.grad is None:
+            assert p.grad is None or float(p.grad.abs().max()) == 0.0, k
+            continue
+        _close(p.grad, q.grad, tol, "grad " + k)

@@ -233,8 +233,25 @@ size_t gsr_set_backward_bytes(int V, int P, const int* K, int two_colors) {
   return BackwardState::bytes_for(total, V, P, two_colors != 0) + carry_bytes(P);
 }
 
-int gsr_set_preprocess(const gsr_set_scene* scene, const gsr_set_state* state, const float* colors2, void* stream) {
-  if (scene == nullptr || state == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
+// What a timed set does not build, checked before anything else (include/gsr.h gsr_set_timed).
+static int check_timed(const gsr_set_scene& sc, const gsr_set_timed& tm) {
+  if (sc.shs != nullptr) return fail(GSR_EINVAL, "%s", "timed view sets take precomputed colours: shs is not built");
+  if (sc.cov3D_precomp != nullptr) return fail(GSR_EINVAL, "%s", "timed view sets: cov3D_precomp is not built");
+  if (tm.means3D_v == nullptr && sc.P > 0) return fail(GSR_EINVAL, "%s", "timed view sets need means3D_v");
+  return GSR_OK;
+}
+// the scene with the timed set's per-view arrays in place of the shared ones (row 0 where a shared array is read)
+static gsr_set_scene timed_scene(const gsr_set_scene& sc, const gsr_set_timed& tm) {
+  gsr_set_scene e = sc;
+  e.means3D = tm.means3D_v;
+  if (tm.scales_v != nullptr) e.scales = tm.scales_v;
+  if (tm.rotations_v != nullptr) e.rotations = tm.rotations_v;
+  return e;
+}
+
+// gsr_set_preprocess; timed != nullptr: gsr_set_timed_preprocess (checked), `scene` already holds the per-view arrays
+static int set_preprocess(const gsr_set_scene* scene, const gsr_set_state* state, const float* colors2,
+                          const gsr_set_timed* timed, void* stream) {
   const gsr_set_scene& sc = *scene;
   const int V = sc.V, P = sc.P;
   if (check_set(V, P) != GSR_OK) return GSR_EINVAL;
@@ -277,7 +294,13 @@ int gsr_set_preprocess(const gsr_set_scene* scene, const gsr_set_state* state, c
   a.col2 = colors2;
   {
     PhaseScope ps(GSR_PHASE_PREPROCESS, s);
-    launch_preprocess(a, cams, g, s);
+    if (timed != nullptr) {
+      const size_t n = (size_t)P;
+      const PreprocessTimed pt = {3 * n, timed->scales_v ? 3 * n : 0, timed->rotations_v ? 4 * n : 0, 3 * n};
+      launch_preprocess(a, cams, g, s, &pt);
+    } else {
+      launch_preprocess(a, cams, g, s);
+    }
   }
   {
     // depth sort of every view's Gaussians (culled last) -> instance counts in depth order, K_v
@@ -294,6 +317,19 @@ int gsr_set_preprocess(const gsr_set_scene* scene, const gsr_set_state* state, c
     launch_binning_counts(V, P, g, s);  // reads the sorted buffer the device flag names (3 or 4 passes)
   }
   return last_launch();
+}
+
+int gsr_set_preprocess(const gsr_set_scene* scene, const gsr_set_state* state, const float* colors2, void* stream) {
+  if (scene == nullptr || state == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
+  return set_preprocess(scene, state, colors2, nullptr, stream);
+}
+
+int gsr_set_timed_preprocess(const gsr_set_scene* scene, const gsr_set_state* state, const gsr_set_timed* timed,
+                             void* stream) {
+  if (scene == nullptr || state == nullptr || timed == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (check_timed(*scene, *timed) != GSR_OK) return GSR_EINVAL;
+  const gsr_set_scene e = timed_scene(*scene, *timed);
+  return set_preprocess(&e, state, timed->colors2_v, timed, stream);
 }
 
 int gsr_composite_forward(int V, int height, int width, const float* color, const float* alpha, const float* bg,
@@ -1166,9 +1202,10 @@ static int grad_chunk_size(int P, int n) {
   return (q + GSR_GRAD_CHUNK_ALIGN - 1) / GSR_GRAD_CHUNK_ALIGN * GSR_GRAD_CHUNK_ALIGN;
 }
 
-int gsr_set_backward(const gsr_set_scene* scene, const gsr_set_state* state, const gsr_set_grads* grads,
-                     void* stream) {
-  if (scene == nullptr || state == nullptr || grads == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
+// gsr_set_backward; timed != nullptr: gsr_set_timed_backward (checked; `scene` holds the per-view arrays, `grads`
+// the second-colour fields of the timed set): the same blend backward, then the per-view per-Gaussian kernel
+static int set_backward(const gsr_set_scene* scene, const gsr_set_state* state, const gsr_set_grads* grads,
+                        const gsr_set_timed* timed, const gsr_set_timed_grads* tgrads, void* stream) {
   const gsr_set_scene& sc = *scene;
   const gsr_set_grads& gr = *grads;
   const int V = sc.V, P = sc.P, width = sc.width, height = sc.height;
@@ -1197,12 +1234,16 @@ int gsr_set_backward(const gsr_set_scene* scene, const gsr_set_state* state, con
   if (P == 0) return last_launch();
   if (K == nullptr || bgs == nullptr || state->geom == nullptr || state->binning == nullptr ||
       state->image == nullptr || gr.work == nullptr || dL_dcolor == nullptr || gr.dL_dmeans2D == nullptr ||
-      gr.dL_dcolors == nullptr || gr.dL_dopacity == nullptr || gr.dL_dmeans3D == nullptr ||
+      gr.dL_dcolors == nullptr || gr.dL_dopacity == nullptr || (timed == nullptr && gr.dL_dmeans3D == nullptr) ||
       state->radii == nullptr || sc.means3D == nullptr)
     return fail(GSR_EINVAL, "%s", "null pointer argument");
   if (sc.shs != nullptr && gr.dL_dsh == nullptr) return fail(GSR_EINVAL, "%s", "dL_dsh required with SHs");
-  if (sc.cov3D_precomp == nullptr && (sc.scales == nullptr || sc.rotations == nullptr || gr.dL_dscales == nullptr ||
-                                      gr.dL_drotations == nullptr))
+  // (a timed set's per-view scales / rotations have per-view gradients: gsr_set_timed_backward checked those)
+  const bool need_dscales = timed == nullptr || timed->scales_v == nullptr;
+  const bool need_drots = timed == nullptr || timed->rotations_v == nullptr;
+  if (sc.cov3D_precomp == nullptr && (sc.scales == nullptr || sc.rotations == nullptr ||
+                                      (need_dscales && gr.dL_dscales == nullptr) ||
+                                      (need_drots && gr.dL_drotations == nullptr)))
     return fail(GSR_EINVAL, "%s", "scales/rotations and their gradients required");
   SetCams cams;
   if (set_cams(sc, cams) != GSR_OK) return GSR_EINVAL;
@@ -1220,7 +1261,7 @@ int gsr_set_backward(const gsr_set_scene* scene, const gsr_set_state* state, con
   const int tres = tile_sort_result(width, height);
   const uint32_t* sorted = tp.packed ? b.key[tres] : b.val[tres];
   GaussBackwardArgs a = shared_args(sc, gr);
-  if (gr.accumulate != 0 && sc.cov3D_precomp == nullptr && dL_dcov3D == nullptr)
+  if (timed == nullptr && gr.accumulate != 0 && sc.cov3D_precomp == nullptr && dL_dcov3D == nullptr)
     return fail(GSR_EINVAL, "%s", "accumulate needs dL_dcov3D: it carries the running dL/dcov3D between calls");
   void* work = gr.work;
   if (gr.work_bytes < carry_bytes(P)) return fail(GSR_EINVAL, "%s", "backward work buffer too small");
@@ -1312,7 +1353,19 @@ int gsr_set_backward(const gsr_set_scene* scene, const gsr_set_state* state, con
     {
       PhaseScope ps(GSR_PHASE_GAUSS_BWD, s);
       const bool last = g1 == V;
-      if (last && gr.n_chunks > 0) {
+      if (timed != nullptr) {
+        TimedGradArgs tv;
+        tv.means_v = timed->means3D_v;
+        tv.scales_v = timed->scales_v;
+        tv.rotations_v = timed->rotations_v;
+        tv.dmeans_v = tgrads->dL_dmeans3D_v;
+        tv.dscales_v = timed->scales_v ? tgrads->dL_dscales_v : nullptr;
+        tv.drotations_v = timed->rotations_v ? tgrads->dL_drotations_v : nullptr;
+        tv.dcolors2_v = two && timed->colors2_v ? tgrads->dL_dcolors2_v : nullptr;
+        tv.dcolors2 = two && !timed->colors2_v ? gr.dL_dcolors2 : nullptr;
+        tv.accumulate = first ? 0 : 1;
+        launch_timed_gauss_backward(a, va, tv, two, s);
+      } else if (last && gr.n_chunks > 0) {
         // the final sums in Gaussian ranges, an event after each (the caller's reduction of a range starts
         // while the next range is computed)
         const int cs = grad_chunk_size(P, gr.n_chunks);
@@ -1331,6 +1384,39 @@ int gsr_set_backward(const gsr_set_scene* scene, const gsr_set_state* state, con
     g0 = g1;
   }
   return last_launch();
+}
+
+int gsr_set_backward(const gsr_set_scene* scene, const gsr_set_state* state, const gsr_set_grads* grads,
+                     void* stream) {
+  if (scene == nullptr || state == nullptr || grads == nullptr) return fail(GSR_EINVAL, "%s", "null pointer argument");
+  return set_backward(scene, state, grads, nullptr, nullptr, stream);
+}
+
+int gsr_set_timed_backward(const gsr_set_scene* scene, const gsr_set_state* state, const gsr_set_grads* grads,
+                           const gsr_set_timed* timed, const gsr_set_timed_grads* timed_grads, void* stream) {
+  if (scene == nullptr || state == nullptr || grads == nullptr || timed == nullptr || timed_grads == nullptr)
+    return fail(GSR_EINVAL, "%s", "null pointer argument");
+  if (check_timed(*scene, *timed) != GSR_OK) return GSR_EINVAL;
+  if (grads->n_chunks > 0) return fail(GSR_EINVAL, "%s", "timed view sets: gradient chunks (n_chunks > 0) are not built");
+  if (grads->colors_override != nullptr)
+    return fail(GSR_EINVAL, "%s", "timed view sets: colors_override is not built (the one-pass two-colour backward only)");
+  const gsr_set_timed& tm = *timed;
+  const gsr_set_timed_grads& tg = *timed_grads;
+  if (tg.dL_dmeans3D_v == nullptr || (tm.scales_v != nullptr && tg.dL_dscales_v == nullptr) ||
+      (tm.rotations_v != nullptr && tg.dL_drotations_v == nullptr) ||
+      (tm.colors2_v != nullptr && tg.dL_dcolors2_v == nullptr))
+    return fail(GSR_EINVAL, "%s", "timed view sets: a per-view array needs its per-view gradient");
+  const gsr_set_scene e = timed_scene(*scene, tm);
+  gsr_set_grads g = *grads;
+  if (tm.colors2_v != nullptr) {
+    // the set's second colours are the per-view ones (in the records): their gradient is per view too
+    if (g.colors2 != nullptr && g.colors2 != tm.colors2_v)
+      return fail(GSR_EINVAL, "%s", "timed view sets: colors2 must be colors2_v (or NULL) when colors2_v is given");
+    if (g.dL_dcolor2 == nullptr) return fail(GSR_EINVAL, "%s", "timed view sets: colors2_v needs dL_dcolor2");
+    g.colors2 = tm.colors2_v;
+    g.dL_dcolors2 = tg.dL_dcolors2_v;  // (non-NULL: selects the two-colour pass; written per view)
+  }
+  return set_backward(&e, state, &g, timed, timed_grads, stream);
 }
 
 int gsr_grad_chunk_range(int P, int n_chunks, int chunk, int* g0, int* g1) {

@@ -52,7 +52,14 @@ struct PreprocessArgs {
   // (GaussRec: b.w, c.w, d.z) so the two-colour blends read it with the record instead of gathering it apart
   const float* col2;
 };
-void launch_preprocess(const PreprocessArgs& a, const SetCams& cams, const GeomState& g, hipStream_t stream);
+// A timed view set (include/gsr.h gsr_set_timed): means3D, scales, rotations and col2 of PreprocessArgs hold one row
+// per view; the element strides between the views' rows (0 = the array is shared by the views)
+struct PreprocessTimed {
+  size_t means, scales, rotations, col2;
+};
+// timed == nullptr: the shared-geometry kernel
+void launch_preprocess(const PreprocessArgs& a, const SetCams& cams, const GeomState& g, hipStream_t stream,
+                       const PreprocessTimed* timed = nullptr);
 
 // Binning — gsr_binning.hip.  order = the depth sort's value buffer (per view: sorted position -> Gaussian).
 void launch_binning_counts(int V, int P, const GeomState& g, hipStream_t stream);
@@ -346,5 +353,19 @@ void launch_laplacian_forward(const MeshRegCall& c, float* lap, void* workspace,
 void launch_laplacian_backward(const MeshRegCall& c, const float* g_lap, float* dxyz, void* workspace,
                                hipStream_t stream);
 void launch_gauss_backward(const GaussBackwardArgs& a, ViewGradArgs va, const AccumArgs& b, hipStream_t stream);
+// Per-Gaussian backward of a timed view set (include/gsr.h gsr_set_timed_backward) — gsr_timed.hip.  The arrays are
+// the whole set's, (V, P, .), indexed by the set's view v0 + v like the geometry state.  scales_v / rotations_v null:
+// that parameter is shared (GaussBackwardArgs::scales / rotations) and its gradient is summed over the views into
+// GaussBackwardArgs::dL_dscales / dL_drotations; otherwise dscales_v / drotations_v receive the per-view rows.  Two
+// colours: exactly one of dcolors2_v (per view) and dcolors2 (P, 3; summed) is given.  Of GaussBackwardArgs only
+// scales, rotations, scale_modifier, dL_dopacity, dL_dcolors, dL_dscales and dL_drotations are used.
+struct TimedGradArgs {
+  const float *means_v, *scales_v, *rotations_v;
+  float *dmeans_v, *dscales_v, *drotations_v, *dcolors2_v;
+  float* dcolors2;
+  int accumulate;  // the shared sums continue from the stored values (a later view group or set)
+};
+void launch_timed_gauss_backward(const GaussBackwardArgs& a, const ViewGradArgs& va, const TimedGradArgs& tv,
+                                 bool two_colors, hipStream_t stream);
 
 }  // namespace gsr

@@ -14,7 +14,8 @@
 
 namespace gsr {
 
-void launch_preprocess_kernel(const PreprocessArgs& a, const SetCams& cams, const GeomState& g, hipStream_t stream);
+void launch_preprocess_kernel(const PreprocessArgs& a, const SetCams& cams, const GeomState& g, hipStream_t stream,
+                              const PreprocessTimed* timed);
 
 // Views handled by one block (the Gaussians' view-independent work and SH staging are shared): the
 // block's 256 threads are 128 Gaussians x 2 halves of the views, so the SH staging (128 x (3M + 1)
@@ -31,10 +32,12 @@ void launch_preprocess_kernel(const PreprocessArgs& a, const SetCams& cams, cons
 // (6 waves per SIMD: 86 -> 79 VGPRs without spills; the LDS allows 6 blocks — 1 % faster)
 // SH_LDS: the SH coefficients are staged (known at compile time, so the SH evaluation reads them with ds_read,
 // not flat loads through a pointer that may point either way)
-template <bool SH_LDS>
-__attribute__((amdgpu_waves_per_eu(6, 8)))
-__global__ __launch_bounds__(256) void k_preprocess(PreprocessArgs a, SetCams cams, GeomState g) {
-  extern __shared__ float s_sh[];  // [128][3M + 1] this block's SH coefficients (odd stride)
+// TIMED: a timed view set (include/gsr.h gsr_set_timed): view v reads row v of the per-view arrays (tv: element
+// strides between views, 0 = the array is shared), so the position, 3D covariance and second colour are formed per
+// view inside the loop; !TIMED compiles to the code of the shared path (tv unused).
+template <bool SH_LDS, bool TIMED>
+__device__ __forceinline__ void preprocess_body(const PreprocessArgs& a, const SetCams& cams, const GeomState& g,
+                                                const PreprocessTimed& tv, float* s_sh) {
   const int nvc = (a.V + GSR_PRE_VIEWS - 1) / GSR_PRE_VIEWS;
   const int vc = blockIdx.x % nvc;
   const int idx0 = (blockIdx.x / nvc) * GSR_PRE_GAUSS;
@@ -74,9 +77,13 @@ __global__ __launch_bounds__(256) void k_preprocess(PreprocessArgs a, SetCams ca
   uint32_t kmn = 0xFFFFFFFFu, kmx = 0u;  // this thread's visible depth keys
 
   // view-independent: position, 3D covariance, opacity, precomputed colour
-  const float3 p_orig = make_float3(a.means3D[3 * ix], a.means3D[3 * ix + 1], a.means3D[3 * ix + 2]);
+  float3 p_orig = make_float3(0.f, 0.f, 0.f);
+  if (!TIMED) p_orig = make_float3(a.means3D[3 * ix], a.means3D[3 * ix + 1], a.means3D[3 * ix + 2]);
   float cov3D[6];
-  if (a.cov3D_precomp != nullptr) {
+  if (TIMED) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) cov3D[i] = 0.f;
+  } else if (a.cov3D_precomp != nullptr) {
 #pragma unroll
     for (int i = 0; i < 6; ++i) cov3D[i] = a.cov3D_precomp[6 * ix + i];
   } else {
@@ -92,7 +99,7 @@ __global__ __launch_bounds__(256) void k_preprocess(PreprocessArgs a, SetCams ca
   const float* my_sh = staged ? s_sh + gl * sstride : a.shs + (size_t)ix * nsh;
   // the two-colour render's second colour, carried in the record's free slots (b.w, c.w, d.z; GaussRec)
   float3 c2 = make_float3(0.f, 0.f, 0.f);
-  if (a.col2 != nullptr) c2 = make_float3(a.col2[3 * ix], a.col2[3 * ix + 1], a.col2[3 * ix + 2]);
+  if (!TIMED && a.col2 != nullptr) c2 = make_float3(a.col2[3 * ix], a.col2[3 * ix + 1], a.col2[3 * ix + 2]);
   const int gx = (a.W + GSR_TILE_X - 1) / GSR_TILE_X;
   const int gy = (a.H + GSR_TILE_Y - 1) / GSR_TILE_Y;
 
@@ -109,6 +116,19 @@ __global__ __launch_bounds__(256) void k_preprocess(PreprocessArgs a, SetCams ca
     for (int i = 0; i < 3; ++i) cpos[i] = ((cfptr)cam.campos)[i];
     const float tanfovx = cam.tanx, tanfovy = cam.tany;
     const float focal_x = cam.fx, focal_y = cam.fy;
+    if (TIMED) {
+      // view v's rows (consecutive Gaussians: coalesced); scales and rotations always given (no cov3D_precomp)
+      const float* m = a.means3D + (size_t)v * tv.means + 3 * (size_t)ix;
+      const float* sv = a.scales + (size_t)v * tv.scales + 3 * (size_t)ix;
+      const float* qv = a.rotations + (size_t)v * tv.rotations + 4 * (size_t)ix;
+      p_orig = make_float3(m[0], m[1], m[2]);
+      cov3d_from_scale_rot(make_float3(sv[0], sv[1], sv[2]), a.scale_modifier, make_float4(qv[0], qv[1], qv[2], qv[3]),
+                           cov3D);
+      if (a.col2 != nullptr) {
+        const float* cv = a.col2 + (size_t)v * tv.col2 + 3 * (size_t)ix;
+        c2 = make_float3(cv[0], cv[1], cv[2]);
+      }
+    }
     int radius = 0;
     uint2 tiles = make_uint2(0u, 0u);
     uint32_t dkey = 0xFFFFFFFFu;  // culled: sorts after every visible depth
@@ -192,6 +212,21 @@ __global__ __launch_bounds__(256) void k_preprocess(PreprocessArgs a, SetCams ca
   }
 }
 
+template <bool SH_LDS>
+__attribute__((amdgpu_waves_per_eu(6, 8)))
+__global__ __launch_bounds__(256) void k_preprocess(PreprocessArgs a, SetCams cams, GeomState g) {
+  extern __shared__ float s_sh[];  // [128][3M + 1] this block's SH coefficients (odd stride)
+  preprocess_body<SH_LDS, false>(a, cams, g, PreprocessTimed{0, 0, 0, 0}, s_sh);
+}
+
+// The preprocess of a timed view set: precomputed colours only (no SH staging, no LDS).  (6 waves per SIMD as the
+// shared kernel: the per-view 3D covariance lives inside the loop, no more registers across it)
+__attribute__((amdgpu_waves_per_eu(6, 8)))
+__global__ __launch_bounds__(256) void k_preprocess_timed(PreprocessArgs a, SetCams cams, GeomState g,
+                                                          PreprocessTimed tv) {
+  preprocess_body<false, true>(a, cams, g, tv, nullptr);
+}
+
 __global__ void k_depth_range_init(uint32_t* drange, unsigned long long col2) {
   drange[threadIdx.x] = 0xFFFFFFFFu;
   drange[64 + threadIdx.x] = 0u;
@@ -215,15 +250,22 @@ __global__ void k_depth_range(uint32_t* drange) {
   }
 }
 
-void launch_preprocess(const PreprocessArgs& a, const SetCams& cams, const GeomState& g, hipStream_t stream) {
+void launch_preprocess(const PreprocessArgs& a, const SetCams& cams, const GeomState& g, hipStream_t stream,
+                       const PreprocessTimed* timed) {
   hipLaunchKernelGGL(k_depth_range_init, dim3(1), dim3(64), 0, stream, g.drange,
                      (unsigned long long)(uintptr_t)(a.P > 0 ? a.col2 : nullptr));
-  if (a.P > 0 && a.V > 0) launch_preprocess_kernel(a, cams, g, stream);
+  if (a.P > 0 && a.V > 0) launch_preprocess_kernel(a, cams, g, stream, timed);
   hipLaunchKernelGGL(k_depth_range, dim3(1), dim3(64), 0, stream, g.drange);
 }
 
-void launch_preprocess_kernel(const PreprocessArgs& a, const SetCams& cams, const GeomState& g, hipStream_t stream) {
+void launch_preprocess_kernel(const PreprocessArgs& a, const SetCams& cams, const GeomState& g, hipStream_t stream,
+                              const PreprocessTimed* timed) {
   const int nvc = (a.V + GSR_PRE_VIEWS - 1) / GSR_PRE_VIEWS;
+  if (timed != nullptr) {
+    hipLaunchKernelGGL(k_preprocess_timed, dim3(nvc * ((a.P + GSR_PRE_GAUSS - 1) / GSR_PRE_GAUSS)), dim3(256), 0,
+                       stream, a, cams, g, *timed);
+    return;
+  }
   const size_t want = a.colors_precomp == nullptr ? (size_t)GSR_PRE_GAUSS * (3 * a.M + 1) : 0;
   const bool sh_lds = a.colors_precomp == nullptr && a.M > 0 && want <= GSR_PRE_LDS_FLOATS;
   const size_t lds = sh_lds ? sizeof(float) * want : 0;

@@ -62,6 +62,16 @@ class SetGrads(ctypes.Structure):
                 + [("accumulate", _i), ("work", _vp), ("work_bytes", _sz), ("n_chunks", _i), ("chunk_events", _vpp)])
 
 
+# A timed view set (gsr_set_timed_preprocess / gsr_set_timed_backward): the per-view (V, P, .) arrays that replace the
+# scene's shared ones, and their per-view gradients.
+class SetTimed(ctypes.Structure):
+    _fields_ = _fields(_vp, "means3D_v scales_v rotations_v colors2_v")
+
+
+class SetTimedGrads(ctypes.Structure):
+    _fields_ = _fields(_vp, "dL_dmeans3D_v dL_dscales_v dL_drotations_v dL_dcolors2_v")
+
+
 # The inputs of the fused SuGaR stages (gsr_sugar_*_forward / _backward take one as their first argument).
 class SugarField(ctypes.Structure):
     _fields_ = (_fields(_i, "M K N R") + _fields(_vp, "x nbr row centers inv_sr strengths min_scale")
@@ -106,7 +116,8 @@ class SugarMeshReg(ctypes.Structure):
 
 
 STRUCTS = {"gsr_set_scene": SetScene, "gsr_set_state": SetState, "gsr_set_outputs": SetOutputs,
-           "gsr_set_grads": SetGrads, "gsr_sugar_field": SugarField, "gsr_sugar_normal": SugarNormal,
+           "gsr_set_grads": SetGrads, "gsr_set_timed": SetTimed, "gsr_set_timed_grads": SetTimedGrads,
+           "gsr_sugar_field": SugarField, "gsr_sugar_normal": SugarNormal,
            "gsr_sugar_mesh": SugarMesh, "gsr_sugar_skin": SugarSkin, "gsr_sugar_timed": SugarTimed,
            "gsr_sugar_arap": SugarArap, "gsr_sugar_spline": SugarSpline, "gsr_sugar_deform": SugarDeform,
            "gsr_sugar_meshreg": SugarMeshReg}
@@ -190,6 +201,8 @@ SIGNATURES = {
     "gsr_set_gauss_state": (_i, [_i, _vp, _i, _vp, _vp, _vp]),
     "gsr_set_render": (_i, [_P(SetScene), _P(SetState), _P(SetOutputs), _vp]),
     "gsr_set_backward": (_i, [_P(SetScene), _P(SetState), _P(SetGrads), _vp]),
+    "gsr_set_timed_preprocess": (_i, [_P(SetScene), _P(SetState), _P(SetTimed), _vp]),
+    "gsr_set_timed_backward": (_i, [_P(SetScene), _P(SetState), _P(SetGrads), _P(SetTimed), _P(SetTimedGrads), _vp]),
     "gsr_grad_chunk_range": (_i, [_i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "gsr_profile_enable": (_i, [_i]),
     "gsr_profile_read": (_i, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong), _i]),

@@ -25,10 +25,14 @@ renderer's epilogue fused on the GPU:
     "sugar_shading" renderer/diff_sugar_rasterizer_shading.py:80-224     two passes (colours, face normals) +
                                                                          point-light material on the blended
                                                                          normals + composite (batched torch)
+    "sugar_temporal" renderer/diff_sugar_rasterizer_temporal.py:82-224   the two passes of "sugar_normal" on frame t
+                                                                         of the timed geometry for view t: one
+                                                                         rasterize_timed_views call per batch
 
 The mode comes from the renderer's ``batch_render_mode`` attribute or, when unset, from the module the
 renderer class is defined in (the reference's file names above).  Any other renderer (st, temporal) keeps the
-reference's per-view loop, still on the HIP rasterizer.
+reference's per-view loop, still on the HIP rasterizer; "sugar_temporal" is opt-in through ``batch_render_mode``
+only (the temporal renderer's module name keeps the loop).
 
 With ``torch.distributed`` initialised, every rank renders its contiguous slice of the batch
 (view_shard.shard_range) and the image outputs are all-gathered (RCCL over xGMI); the per-view lists
@@ -56,7 +60,7 @@ from .cameras import get_cam_info_gaussian
 from . import view_shard
 from .view_shard import _world, all_gather_views, shard_range
 
-MODES = ("plain", "background", "advanced", "shading", "normal", "sugar_normal", "sugar_shading")
+MODES = ("plain", "background", "advanced", "shading", "normal", "sugar_normal", "sugar_shading", "sugar_temporal")
 _MODULE_MODES = {
     "diff_gaussian_rasterizer": "plain",
     "diff_gaussian_rasterizer_background": "background",
@@ -103,6 +107,12 @@ def _rasterize_views(*args, **kwargs):
     from .batched import rasterize_views
 
     return rasterize_views(*args, **kwargs)
+
+
+def _rasterize_timed_views(*args, **kwargs):
+    from .batched import rasterize_timed_views
+
+    return rasterize_timed_views(*args, **kwargs)
 
 
 def _shade_views(*args, **kwargs):
@@ -363,6 +373,32 @@ def render_views_local(renderer, batch: dict, mode: str, lo: int, hi: int, draws
             mask = alpha > 0.99
             out.update(comp_rgb=color, comp_normal=nmap,
                        comp_depth=torch.where(mask, depth, depth.detach()), comp_mask=alpha)
+        elif mode == "sugar_temporal":
+            if reduce is not None:
+                raise ValueError("sugar_temporal: the in-backward gradient reduction is not built for timed sets; "
+                                 "reduce after the backward (view_shard.allreduce_grads)")
+            # the background is always inverted, without a draw (renderer/diff_sugar_rasterizer_temporal.py:97-104)
+            settings = _settings(pc, cams, [1.0 - renderer.background_tensor] * n, H, W, scaling_modifier)
+            # the views' timestamps / frame indices as the loop's cameras carry them (view_camera), all frames of the
+            # slice from one call of the geometry instead of one per view (:150, :180-182)
+            ts = batch["timestamp"][lo:hi] if "timestamp" in batch else None
+            fi = batch["frame_indices"][lo:hi] if "frame_indices" in batch else None
+            attrs = pc.get_timed_gs_attributes(ts, fi)
+            frame_normals = pc.get_timed_gs_normals(ts, fi)
+            # (geometry/dynamic_sugar.py get_timed_gs_all_single_time: static scales unless d_scale)
+            scales = attrs["scale"] if getattr(pc.cfg, "d_scale", False) else pc.get_scaling
+            # both rasterizer calls (:156-165 colours, :183-192 the frame's face normals with a zero means2D) of
+            # every frame from one timed view set: view t renders frame t
+            color, radii, depth, alpha, normal = _rasterize_timed_views(
+                settings, attrs["xyz"], m2, pc.get_opacity, pc.get_points_rgb(), scales, attrs["rotation"],
+                colors2=frame_normals, clamp=True)
+            if batch.get("compute_normal_from_dist", True):
+                _, nmap_dist = _depth_normal_views(depth, alpha, batch["rays_o"][lo:hi], batch["rays_d"][lo:hi])
+                out["comp_normal_from_dist"] = nmap_dist
+            nmap = _sugar_normal_map(normal, alpha)
+            mask = alpha > 0.99
+            out.update(comp_rgb=color, comp_normal=nmap,
+                       comp_depth=torch.where(mask, depth, depth.detach()), comp_mask=alpha)
         elif mode == "sugar_shading":
             zero = [renderer.background_tensor * 0] * n
             settings = _settings(pc, cams, zero, H, W, scaling_modifier)
@@ -394,7 +430,8 @@ def _mode_keys(renderer, mode):
             "shading": ["comp_rgb", "comp_normal", "comp_depth", "comp_mask"],
             "normal": ["comp_rgb", "comp_normal", "comp_depth", "comp_mask"],
             "sugar_normal": ["comp_rgb", "comp_normal", "comp_depth", "comp_mask"],
-            "sugar_shading": ["comp_rgb", "comp_normal", "comp_depth", "comp_mask"]}[mode]
+            "sugar_shading": ["comp_rgb", "comp_normal", "comp_depth", "comp_mask"],
+            "sugar_temporal": ["comp_rgb", "comp_normal", "comp_depth", "comp_mask"]}[mode]
     if mode in ("shading", "normal") and getattr(renderer.geometry.cfg, "pred_normal", False):
         keys.append("comp_pred_normal")
     return keys
@@ -409,7 +446,7 @@ def render_batch(renderer, batch: dict, mode: str, group=None, shard: bool = Tru
     H, W = int(batch["height"]), int(batch["width"])
     dev, dtype = renderer.geometry.get_xyz.device, renderer.geometry.get_xyz.dtype
     keys = _mode_keys(renderer, mode)
-    if mode == "sugar_normal" and batch.get("compute_normal_from_dist", True):
+    if mode in ("sugar_normal", "sugar_temporal") and batch.get("compute_normal_from_dist", True):
         keys.append("comp_normal_from_dist")
     outputs = {"viewspace_points": local["viewspace_points"], "visibility_filter": local["visibility_filter"],
                "radii": local["radii"]}

@@ -340,3 +340,219 @@ def rasterize_views(settings_list, means3D, means2D_list, opacities, shs=None, c
     return _RasterizeViews.apply(list(settings_list), grad_reduce, two_color_backward, bool(clamp), means3D, shs,
                                  colors_precomp, opacities, scales, rotations, cov3D_precomp, background, colors2,
                                  *means2D_list)
+
+
+class _RasterizeTimedViews(torch.autograd.Function):
+    """rasterize_timed_views: the view sets of _RasterizeViews with per-view geometry (include/gsr.h gsr_set_timed)."""
+
+    @staticmethod
+    def forward(ctx, settings_list, clamp, means3D, colors_precomp, opacities, scales, rotations, composite_bg, colors2,
+                *means2D):
+        lib = _C.load_library()
+        V = len(settings_list)
+        dev = means3D.device
+        P = int(means3D.shape[1])
+        s0 = settings_list[0]
+        H, W = int(s0.image_height), int(s0.image_width)
+        f = lambda t, n: _C._f32(t, n, dev)  # noqa: E731
+        keep = lambda t: t.detach().contiguous()  # noqa: E731  (fp32 on `dev`: rasterize_timed_views checked)
+        m3, col, op, sc, rot = keep(means3D), keep(colors_precomp), keep(opacities), keep(scales), keep(rotations)
+        c2 = keep(colors2) if colors2 is not None else None
+        sc_v, rot_v, c2_v = sc.dim() == 3, rot.dim() == 3, c2 is not None and c2.dim() == 3
+        p = _C._ptr
+        stream = _C._stream(dev)
+        fopt = dict(dtype=torch.float32, device=dev)
+        color = torch.empty((V, 3, H, W), **fopt)
+        cbg = None
+        clamp_only = bool(clamp) and composite_bg is None
+        if composite_bg is not None:
+            cbg = _C._f32(composite_bg, "background", dev).reshape(V, H, W, 3)
+        fused_out = cbg is not None or clamp_only
+        render = torch.empty((V, 3, H, W), **fopt) if fused_out else None
+        depth = torch.empty((V, 1, H, W), **fopt)
+        alpha = torch.empty((V, 1, H, W), **fopt)
+        color2 = torch.empty((V, 3, H, W), **fopt) if c2 is not None else None
+        radii = torch.empty((V, P), dtype=torch.int32, device=dev)
+        sets = []
+        # what the views share goes into the scene; the per-view arrays into the set's gsr_set_timed
+        gaussians = dict(means3D=None, scales=None if sc_v else sc, rotations=None if rot_v else rot, opacities=op,
+                         shs=None, colors_precomp=col, cov3D_precomp=None)
+        for lo in range(0, V, SET_MAX):
+            hi = min(V, lo + SET_MAX)
+            cams = [(f(s.viewmatrix, "viewmatrix"), f(s.projmatrix, "projmatrix"), f(s.campos, "campos"),
+                     f(s.bg, "bg")) for s in settings_list[lo:hi]]
+            vs = _ViewSet(lo, hi, cams, [float(s.tanfovx) for s in settings_list[lo:hi]],
+                          [float(s.tanfovy) for s in settings_list[lo:hi]], gaussians, radii[lo:hi], P=P,
+                          degree=int(s0.sh_degree), M=0, width=W, height=H, prefiltered=int(bool(s0.prefiltered)),
+                          scale_modifier=float(s0.scale_modifier))
+            vs.timed = _C.SetTimed(means3D_v=_addr(m3[lo:hi]), scales_v=_addr(sc[lo:hi]) if sc_v else None,
+                                   rotations_v=_addr(rot[lo:hi]) if rot_v else None,
+                                   colors2_v=_addr(c2[lo:hi]) if c2_v else None)
+            vs.allocate(geom=torch.empty(int(lib.gsr_set_geom_bytes(vs.V, P)), dtype=torch.uint8, device=dev))
+            _C._check(lib.gsr_set_timed_preprocess(vs.scene, vs.state, vs.timed, stream))
+            sets.append(vs)
+        for vs in sets:
+            K = (ctypes.c_int * vs.V)()
+            L = (ctypes.c_int * vs.V)()
+            # the one host sync of the set: the instance counts size the binning buffers
+            _C._check(lib.gsr_set_num_rendered(vs.V, p(vs.geom), P, K, None, L, stream))
+            vs.K = list(K)
+            _C.RECENT_LISTED.extend(L)
+            _C.RECENT_FORWARDS.extend((k, H, W) for k in vs.K)
+            vs.state.num_rendered = K
+            vs.allocate(
+                binning=torch.empty(int(lib.gsr_set_binning_bytes(vs.V, P, K, W, H)), dtype=torch.uint8, device=dev),
+                image=torch.empty(int(lib.gsr_set_image_bytes(vs.V, P, K, W, H, int(c2 is not None))),
+                                  dtype=torch.uint8, device=dev))
+            sl = slice(vs.lo, vs.hi)
+            out = _C.SetOutputs(out_color=_addr(color[sl]), out_depth=_addr(depth[sl]), out_alpha=_addr(alpha[sl]))
+            if cbg is not None:
+                out.bg_images = _addr(cbg[sl])
+            if fused_out:
+                out.out_render = _addr(render[sl])
+            if c2 is not None:
+                # per view: the pointer the preprocess embedded (the blends read the records); shared: gathered
+                out.colors2, out.out_color2 = _addr(c2[sl]) if c2_v else _addr(c2), _addr(color2[sl])
+            _C._check(lib.gsr_set_render(vs.scene, vs.state, out, stream))
+        ctx.settings = settings_list
+        ctx.sets = sets
+        ctx.bg_shape = tuple(composite_bg.shape) if composite_bg is not None else None
+        ctx.save_for_backward(m3, col, sc, rot, radii, cbg, color if fused_out else None, c2)
+        ctx.mark_non_differentiable(radii)
+        if c2 is not None:
+            return (render if fused_out else color), radii, depth, alpha, color2
+        return (render if fused_out else color), radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, g_color, _g_radii, g_depth, g_alpha, g_color2=None):
+        lib = _C.load_library()
+        m3, col, sc, rot, radii, cbg, color, c2 = ctx.saved_tensors
+        V, P = int(m3.shape[0]), int(m3.shape[1])
+        dev = m3.device
+        fopt = dict(dtype=torch.float32, device=dev)
+        second = c2 is not None and g_color2 is not None
+        sc_v, rot_v, c2_v = sc.dim() == 3, rot.dim() == 3, c2 is not None and c2.dim() == 3
+        # per-view rows are always overwritten by the kernel; the shared sums too (accumulate continues them)
+        d_m2 = torch.empty((V, P, 3), **fopt)
+        d_m3 = torch.empty_like(m3)
+        d_sc, d_rot = torch.empty_like(sc), torch.empty_like(rot)
+        d_op, d_col = torch.empty((P, 1), **fopt), torch.empty((P, 3), **fopt)
+        d_c2 = (torch.empty_like(c2) if second else torch.zeros_like(c2)) if c2 is not None else None
+        d_bg = torch.empty_like(cbg) if cbg is not None and ctx.needs_input_grad[7] else None
+        if P == 0:
+            for t in (d_m2, d_m3, d_sc, d_rot, d_op, d_col, d_c2, d_bg):
+                if t is not None:
+                    t.zero_()
+        else:
+            gc = g_color.float().contiguous()
+            gd = g_depth.float().contiguous() if g_depth is not None else None
+            ga = g_alpha.float().contiguous() if g_alpha is not None else None
+            g2 = g_color2.float().contiguous() if second else None
+            stream = _C._stream(dev)
+            g = _C.SetGrads(dL_dcolors=_addr(d_col), dL_dopacity=_addr(d_op), dL_dscales=None if sc_v else _addr(d_sc),
+                            dL_drotations=None if rot_v else _addr(d_rot))
+            for si, vs in enumerate(ctx.sets):
+                kmax = _arr(ctypes.c_int, [max(vs.K)])
+                need = int(lib.gsr_set_backward_bytes(vs.V, P, vs.state.num_rendered, int(second)))
+                largest = int(lib.gsr_set_backward_bytes(1, P, kmax, int(second)))
+                work = torch.empty(max(largest, min(need, WORK_BUDGET)), dtype=torch.uint8, device=dev)
+                sl = slice(vs.lo, vs.hi)
+                g.dL_dcolor, g.dL_dmeans2D = _addr(gc[sl]), _addr(d_m2[sl])
+                g.dL_ddepth = _addr(gd[sl]) if gd is not None else None
+                g.dL_dalpha = _addr(ga[sl]) if ga is not None else None
+                g.color = _addr(color[sl]) if color is not None else None
+                g.bg_images = _addr(cbg[sl]) if cbg is not None else None
+                g.dL_dbg = _addr(d_bg[sl]) if d_bg is not None else None
+                timed = vs.timed
+                if second:
+                    g.dL_dcolor2 = _addr(g2[sl])
+                    if not c2_v:
+                        g.colors2, g.dL_dcolors2 = _addr(c2), _addr(d_c2)
+                elif c2_v:
+                    # the second colour's image took no gradient: the one-colour backward of the first call
+                    timed = _C.SetTimed.from_buffer_copy(vs.timed)
+                    timed.colors2_v = None
+                tg = _C.SetTimedGrads(dL_dmeans3D_v=_addr(d_m3[sl]), dL_dscales_v=_addr(d_sc[sl]) if sc_v else None,
+                                      dL_drotations_v=_addr(d_rot[sl]) if rot_v else None,
+                                      dL_dcolors2_v=_addr(d_c2[sl]) if second and c2_v else None)
+                g.accumulate = 1 if si > 0 else 0
+                g.work, g.work_bytes = _addr(work), work.numel()
+                _C._check(lib.gsr_set_timed_backward(vs.scene, vs.state, g, timed, tg, stream))
+        if d_bg is not None:
+            d_bg = d_bg.reshape(ctx.bg_shape)
+        grads = [None, None, d_m3, d_col, d_op, d_sc, d_rot, d_bg, d_c2] + [d_m2[v] for v in range(V)]
+        for k, need in enumerate(ctx.needs_input_grad):
+            if not need:
+                grads[k] = None
+        return tuple(grads)
+
+
+def _timed_shape(name, t, V, P, width, per_view_only=False):
+    """ValueError unless t is (V, P, width) or, when allowed, (P, width)."""
+    ok = tuple(t.shape) == (V, P, width) or (not per_view_only and tuple(t.shape) == (P, width))
+    if not ok:
+        want = f"({V}, {P}, {width})" + ("" if per_view_only else f" or ({P}, {width})")
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {want}")
+
+
+def rasterize_timed_views(settings_list, means3D, means2D_list, opacities, colors_precomp, scales, rotations,
+                          colors2=None, background=None, clamp=False, grad_reduce=None):
+    """Render V views that each carry their own frame of the Gaussians' geometry — frame v of a time batch from camera
+    v, as the timed renderers do with one rasterizer call per frame (renderer/diff_sugar_rasterizer_temporal.py:150-192,
+    renderer/diff_gaussian_rasterizer_st.py) — as view sets: one launch per stage and one host sync per set.
+
+    means3D (V, P, 3); scales (V, P, 3) or (P, 3); rotations (V, P, 4) or (P, 4); colors2 (V, P, 3), (P, 3) or None;
+    opacities (P, 1) and colors_precomp (P, 3) are shared by the views.  fp32 tensors on one GPU.  Frame t of
+    sugar_dynamic.timed_gaussians' outputs is view t: ``means3D=xyz, rotations=rotation, colors2=normals``.
+
+    Outputs, means2D_list, background, clamp and colors2 as for rasterize_views: (color, radii, depth, alpha
+    [, color2]).  Gradients: a per-view input receives per-view rows (exactly zero where the view's blend did not
+    reach the Gaussian), a shared one the sum over the views; a repeated backward (retain_graph) gives the same bits.
+
+    Not built: shs, cov3D_precomp, per-view opacities / colours, the separate two-colour backward, and the in-backward
+    rank reduction (grad_reduce raises: reduce after the backward, as view_shard.allreduce_grads does)."""
+    if grad_reduce is not None:
+        raise ValueError("rasterize_timed_views: the in-backward reduction (grad_reduce) is not built for timed sets; "
+                         "reduce the gradients after the backward (view_shard.allreduce_grads)")
+    if not settings_list:
+        raise ValueError("at least one view")
+    V = len(settings_list)
+    if len(means2D_list) != V:
+        raise ValueError("one means2D placeholder per view")
+    if means3D.dim() != 3 or means3D.shape[0] != V or means3D.shape[2] != 3:
+        raise ValueError(f"means3D has shape {tuple(means3D.shape)}, expected ({V}, P, 3): one frame per view")
+    P = int(means3D.shape[1])
+    if scales is None or rotations is None or colors_precomp is None or opacities is None:
+        raise ValueError("rasterize_timed_views needs opacities, colors_precomp, scales and rotations")
+    _timed_shape("scales", scales, V, P, 3)
+    _timed_shape("rotations", rotations, V, P, 4)
+    if colors2 is not None:
+        _timed_shape("colors2", colors2, V, P, 3)
+    if tuple(colors_precomp.shape) != (P, 3):
+        raise ValueError(f"colors_precomp has shape {tuple(colors_precomp.shape)}, expected ({P}, 3): shared by the views")
+    if opacities.numel() != P:
+        raise ValueError(f"opacities has {opacities.numel()} elements, expected {P}: shared by the views")
+    for m2 in means2D_list:
+        if tuple(m2.shape) != (P, 3):
+            raise ValueError(f"a means2D placeholder has shape {tuple(m2.shape)}, expected ({P}, 3)")
+    s0 = settings_list[0]
+    H, W = int(s0.image_height), int(s0.image_width)
+    if any(int(s.image_height) != H or int(s.image_width) != W for s in settings_list):
+        raise ValueError("all views of a batch must have the same image size")
+    if any(int(s.sh_degree) != int(s0.sh_degree) or float(s.scale_modifier) != float(s0.scale_modifier)
+           or bool(s.prefiltered) != bool(s0.prefiltered) for s in settings_list):
+        raise ValueError("sh_degree, scale_modifier and prefiltered must be shared by the views of a batch")
+    if background is not None and background.numel() != V * H * W * 3:
+        raise ValueError("background must hold (V, H, W, 3) values")
+    named = [("means3D", means3D), ("opacities", opacities), ("colors_precomp", colors_precomp), ("scales", scales),
+             ("rotations", rotations), ("colors2", colors2)]
+    for name, t in named:
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"{name} is {t.dtype}, expected torch.float32")
+    if means3D.device.type != "cuda":
+        raise ValueError("rasterize_timed_views requires tensors on a ROCm GPU (device 'cuda'): there is no CPU path")
+    for name, t in named + [("background", background)]:
+        if t is not None and t.device != means3D.device:
+            raise ValueError(f"{name} is on {t.device}, expected {means3D.device}")
+    return _RasterizeTimedViews.apply(list(settings_list), bool(clamp), means3D, colors_precomp, opacities, scales,
+                                      rotations, background, colors2, *means2D_list)
