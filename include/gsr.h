@@ -91,7 +91,9 @@ const char* gsr_version(void);
  *      gsr_sugar_laplacian_forward / _backward (SuGaR: the normal-consistency and uniform-Laplacian regularisers of the
  *      deformed surface mesh, for all frames of a batch);
  *      gsr_set_timed / gsr_set_timed_grads and gsr_set_timed_preprocess / gsr_set_timed_backward (timed view sets: every
- *      view of a set renders its own frame of the Gaussians' geometry, e.g. the frames of dynamic SuGaR).
+ *      view of a set renders its own frame of the Gaussians' geometry, e.g. the frames of dynamic SuGaR);
+ *      gsr_densify_batch and gsr_densify_stats (the densification statistics of a view batch — running maximum of the
+ *      radii, sum of the screen-space gradient norms and visibility count — in one launch).
  */
 #define GSR_ABI_VERSION 9
 int gsr_abi_version(void);
@@ -359,6 +361,42 @@ int gsr_set_timed_preprocess(const gsr_set_scene* scene, const gsr_set_state* st
 /* gsr_set_backward of a timed set (after gsr_set_timed_preprocess + gsr_set_render with the same arrays). */
 int gsr_set_timed_backward(const gsr_set_scene* scene, const gsr_set_state* state, const gsr_set_grads* grads,
                            const gsr_set_timed* timed, const gsr_set_timed_grads* timed_grads, void* stream);
+
+/*
+ * Densification statistics of a view batch: what the reference's GaussianBaseModel.update_states
+ * (geometry/gaussian_base.py:845-851) accumulates view by view after the backward, for V <= GSR_SET_MAX views in one
+ * launch.  Per Gaussian p, from the running values m = max_radii[p], s = grad_norm_sum[p], c = count[p] (accumulate 1)
+ * or from zero (accumulate 0), for v = 0 .. V-1 in this order:
+ *     m = max(m, (float)radii[v][p])                       (a NaN already in m stays, as torch.max keeps it)
+ *     seen = visible[v] ? visible[v][p] != 0 : radii[v][p] > 0
+ *     if seen:  s = s + sqrt(x * x + y * y)  with x = grads[v][3p], y = grads[v][3p + 1]   (skipped: grads[v] NULL)
+ *               c = c + 1
+ * in fp32, every operation rounded on its own (no fused multiply-add) and the square root correctly rounded: the bits
+ * of the fp32 composition (gx * gx + gy * gy).sqrt() of IEEE operations, added view after view.  The update is
+ * sequential and in place,
+ * so a batch of more than GSR_SET_MAX views is several calls in view order with accumulate = 1, with the bits of one
+ * call.  No atomics: two calls give the same bits.
+ *   radii    V rows of P int32 (gsr_set_state.radii rows)
+ *   grads    V rows of (P,3) float (the screen-space gradient rows, gsr_set_grads.dL_dmeans2D); an entry may be NULL
+ *            (no gradient reached that view: it still counts)
+ *   visible  V rows of P bytes, or all NULL: visible = radii > 0
+ * The arrays are device memory; the struct is read during the call and no pointer to it is kept.  Entries past V are
+ * ignored.  P == 0 or V == 0 launches nothing and leaves the three arrays as they are (also with accumulate 0).
+ * GSR_EINVAL, before any device work: V outside 0..GSR_SET_MAX, P < 0, a NULL radii row, a NULL output, visibility
+ * rows that are partly NULL.
+ */
+/* (tables of one device pointer per view, held in the struct itself: GSR_SET_MAX entries each) */
+typedef const int* gsr_view_rows_i32[GSR_SET_MAX];
+typedef const float* gsr_view_rows_f32[GSR_SET_MAX];
+typedef const unsigned char* gsr_view_rows_u8[GSR_SET_MAX];
+typedef struct gsr_densify_batch {
+  int V, P, accumulate;                       /* accumulate 0: start from zero; 1: from the arrays' contents */
+  gsr_view_rows_i32 radii;
+  gsr_view_rows_f32 grads;
+  gsr_view_rows_u8 visible;
+  float *max_radii, *grad_norm_sum, *count;   /* P each */
+} gsr_densify_batch;
+int gsr_densify_stats(const gsr_densify_batch* in, void* stream);
 
 /*
  * Optional phase timing with HIP events recorded on the launch stream around each phase's kernels.

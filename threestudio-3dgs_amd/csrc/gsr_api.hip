@@ -1025,6 +1025,26 @@ int gsr_sugar_laplacian_backward(const gsr_sugar_meshreg* in, const float* dL_dl
   return last_launch();
 }
 
+// ---- the densification statistics of a view batch (gsr_densify.hip) ---------------------------------
+int gsr_densify_stats(const gsr_densify_batch* in, void* stream) {
+  if (in == nullptr) return null_argument();
+  if (in->V < 0 || in->V > GSR_SET_MAX) return fail(GSR_EINVAL, "%s", "a densification call takes 0..64 views");
+  if (in->P < 0) return fail(GSR_EINVAL, "%s", "P must be >= 0");
+  if (in->P == 0 || in->V == 0) return nothing_to_do();
+  if (in->max_radii == nullptr) return null_named("max_radii");
+  if (in->grad_norm_sum == nullptr) return null_named("grad_norm_sum");
+  if (in->count == nullptr) return null_named("count");
+  int with_rows = 0;
+  for (int v = 0; v < in->V; ++v) {
+    if (in->radii[v] == nullptr) return null_named("radii row");
+    with_rows += in->visible[v] != nullptr;
+  }
+  if (with_rows != 0 && with_rows != in->V)
+    return fail(GSR_EINVAL, "%s", "visibility rows must be given for every view or for none");
+  launch_densify_stats(*in, (hipStream_t)stream);
+  return last_launch();
+}
+
 // ---- the view-segmented radix sort (tests: every sort of the library runs seg_sort) -----------------
 struct SortWork {
   uint32_t *keys2, *vals2, *counts, *totals;

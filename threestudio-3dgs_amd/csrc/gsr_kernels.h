@@ -368,4 +368,8 @@ struct TimedGradArgs {
 void launch_timed_gauss_backward(const GaussBackwardArgs& a, const ViewGradArgs& va, const TimedGradArgs& tv,
                                  bool two_colors, hipStream_t stream);
 
+// The densification statistics of a view batch (include/gsr.h gsr_densify_stats) — gsr_densify.hip.  The struct is the
+// kernel argument (the row pointer tables by value); visible[0] selects the visibility-row variant.
+void launch_densify_stats(const gsr_densify_batch& a, hipStream_t stream);
+
 }  // namespace gsr

@@ -115,7 +115,16 @@ class SugarMeshReg(ctypes.Structure):
     _fields_ = _fields(_i, "T V E P") + _fields(_vp, "vert_xyz pairs slot_offsets slots ring_offsets ring")
 
 
-STRUCTS = {"gsr_set_scene": SetScene, "gsr_set_state": SetState, "gsr_set_outputs": SetOutputs,
+SET_MAX = 64  # include/gsr.h GSR_SET_MAX
+
+
+# The densification statistics of a view batch (gsr_densify_stats): tables of one row pointer per view, in the struct.
+class DensifyBatch(ctypes.Structure):
+    _fields_ = (_fields(_i, "V P accumulate") + _fields(_vp * SET_MAX, "radii grads visible")
+                + _fields(_vp, "max_radii grad_norm_sum count"))
+
+
+STRUCTS = {"gsr_densify_batch": DensifyBatch, "gsr_set_scene": SetScene, "gsr_set_state": SetState, "gsr_set_outputs": SetOutputs,
            "gsr_set_grads": SetGrads, "gsr_set_timed": SetTimed, "gsr_set_timed_grads": SetTimedGrads,
            "gsr_sugar_field": SugarField, "gsr_sugar_normal": SugarNormal,
            "gsr_sugar_mesh": SugarMesh, "gsr_sugar_skin": SugarSkin, "gsr_sugar_timed": SugarTimed,
@@ -203,6 +212,7 @@ SIGNATURES = {
     "gsr_set_backward": (_i, [_P(SetScene), _P(SetState), _P(SetGrads), _vp]),
     "gsr_set_timed_preprocess": (_i, [_P(SetScene), _P(SetState), _P(SetTimed), _vp]),
     "gsr_set_timed_backward": (_i, [_P(SetScene), _P(SetState), _P(SetGrads), _P(SetTimed), _P(SetTimedGrads), _vp]),
+    "gsr_densify_stats": (_i, [_P(DensifyBatch), _vp]),
     "gsr_grad_chunk_range": (_i, [_i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "gsr_profile_enable": (_i, [_i]),
     "gsr_profile_read": (_i, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong), _i]),
