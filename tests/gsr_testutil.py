@@ -402,6 +402,35 @@ def _gpu_views(scene, cams, bgs, ups=None, background=None):
     return out
 
 
+def _image_state(scene, cam):
+    """One per-view forward's image state: (split_mode bytes [0] != 0: the forward wrote the split backward's
+    checkpoints, [1] = 1: the tile-wave forward's quadrant masks, 2: the quadrant-wave forward's; quad_maxc
+    (tiles, 4))."""
+    import torch
+
+    from diff_gaussian_rasterization import _C
+
+    dev = "cuda"
+    t = {k: torch.tensor(scene[k], device=dev) for k in ("means3D", "opacities", "scales", "rotations", "shs")}
+    with torch.no_grad():
+        out = _C.rasterize_gaussians(torch.zeros(3, device=dev), t["means3D"], None, t["opacities"], t["scales"],
+                                     t["rotations"], 1.0, None, torch.tensor(cam["view"], device=dev),
+                                     torch.tensor(cam["proj"], device=dev), cam["tanx"], cam["tany"], cam["H"],
+                                     cam["W"], t["shs"], int(scene["sh_degree"]), torch.tensor(cam["campos"], device=dev),
+                                     False, False)
+    image = out[7].cpu().numpy()
+    tiles = ((cam["W"] + 15) // 16) * ((cam["H"] + 15) // 16)
+    # csrc/gsr_common.h ImageState: split_mode (one 256-byte unit), ranges, then quad_maxc
+    off = 256 + (8 * tiles + 255) // 256 * 256
+    mode = image[:8].view(np.uint32) & 0xff
+    return (int(mode[0]), int(mode[1])), image[off:off + 16 * tiles].view(np.uint32).reshape(tiles, 4).copy()
+
+
+def _quad_maxc(scene, cam):
+    """Per tile, the deepest blended list position of its quadrants (the image state's quad_maxc)."""
+    return _image_state(scene, cam)[1].max(1)
+
+
 def _view(out, v):
     return dict(color=out["color"][v], depth=out["depth"][v], alpha=out["alpha"][v], radii=out["radii"][v])
 

@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 
 import oracle
-from gsr_testutil import (GRAD_KEYS, SUGAR_OUT, _composite, _composite_upstream, _gpu_views, _settings,
+from gsr_testutil import (GRAD_KEYS, SUGAR_OUT, _composite, _composite_upstream, _gpu_views, _quad_maxc, _settings,
                           _sugar_epilogue, _sum_grads, _view, adjudicate, check_forward, check_grads, check_radii, flip_excuse, gs, make_camera,
                           oracle_cam, print_report, run_oracle)
 
@@ -238,27 +238,6 @@ def _deep_scene():
     """Many faint Gaussians in a small image: tiles blend well past GSR_SPLIT_NCK x GSR_SPLIT_CH candidates."""
     scene = gs.make_scene(80_000, sh_degree=1, seed=71, scale_mult=2.0, opacity_range=(0.005, 0.03))
     return scene, make_camera(80, 64, azimuth=25.0)
-
-
-def _quad_maxc(scene, cam):
-    """Per tile, the deepest blended list position of its quadrants (the image state's quad_maxc)."""
-    import torch
-
-    from diff_gaussian_rasterization import _C
-
-    dev = "cuda"
-    t = {k: torch.tensor(scene[k], device=dev) for k in ("means3D", "opacities", "scales", "rotations", "shs")}
-    with torch.no_grad():
-        out = _C.rasterize_gaussians(torch.zeros(3, device=dev), t["means3D"], None, t["opacities"], t["scales"],
-                                     t["rotations"], 1.0, None, torch.tensor(cam["view"], device=dev),
-                                     torch.tensor(cam["proj"], device=dev), cam["tanx"], cam["tany"], cam["H"],
-                                     cam["W"], t["shs"], int(scene["sh_degree"]), torch.tensor(cam["campos"], device=dev),
-                                     False, False)
-    image = out[7].cpu().numpy()
-    tiles = ((cam["W"] + 15) // 16) * ((cam["H"] + 15) // 16)
-    # csrc/gsr_common.h ImageState: split_mode (one 256-byte unit), ranges, then quad_maxc
-    off = 256 + (8 * tiles + 255) // 256 * 256
-    return image[off:off + 16 * tiles].view(np.uint32).reshape(tiles, 4).max(1)
 
 
 @pytest.mark.parametrize("size", ["listed", "overflow"])
