@@ -118,20 +118,28 @@ def test_identical_frames_equal_the_shared_set():
     _within_bar(got["g_means2D"], np.stack(want["g_means2D"]), "means2D")
 
 
-@pytest.mark.parametrize("V,knob,value", [(5, "SET_MAX", 2), (6, "WORK_BUDGET", 1)])
-def test_sets_and_view_groups_are_bitwise_invariant(V, knob, value, monkeypatch):
+@pytest.mark.parametrize("V,knob,value,background", [
+    pytest.param(5, "SET_MAX", 2, False, id="5-SET_MAX-2"),
+    pytest.param(6, "WORK_BUDGET", 1, False, id="6-WORK_BUDGET-1"),
+    pytest.param(5, "SET_MAX", 2, True, id="5-SET_MAX-2-background")])
+def test_sets_and_view_groups_are_bitwise_invariant(V, knob, value, background, monkeypatch):
     """Split into sets of 2 views (SET_MAX) or into one-view backward groups (WORK_BUDGET = 1): every gradient has the
-    bits of the single set / single group."""
+    bits of the single set / single group.  background: the fused composite instead of the clamp, so each set takes its
+    own slice of the background images and of dL/dbg."""
     from diff_gaussian_rasterization import batched
 
     cams, ups = _cams(V), _ups(V, seed=80)
     ups2 = [gs.upstream_grads(56, 72, seed=95 + v)[0] for v in range(V)]
     frames = tf.make_frames(P, cams, 44)
     bgs = [BGS[v % 4] for v in range(V)]
-    kw = dict(two=True, ups2=ups2, shared_scales=True, clamp=True)
+    kw = dict(two=True, ups2=ups2, shared_scales=True, clamp=not background)
+    if background:
+        kw["background"] = np.random.default_rng(5).random((V, 56, 72, 3)).astype(np.float32)
+        bgs = [[0.0, 0.0, 0.0]] * V
     one = tf.run_timed(frames, cams, bgs, ups, **kw)
     monkeypatch.setattr(batched, knob, value)
     split = tf.run_timed(frames, cams, bgs, ups, **kw)
+    assert ("g_background" in one) == background
     for k in one:
         if k != "K":
             assert np.array_equal(one[k], split[k]), k

@@ -2,6 +2,7 @@
 rasterize_timed_views, and the batch renderer's "sugar_temporal" mode on the torch stand-ins."""
 import ctypes
 import random
+import types
 
 import numpy as np
 import pytest
@@ -60,6 +61,76 @@ def test_entry_points_reject_what_is_not_built():
     assert b"per-view gradient" in err(lib.gsr_set_timed_backward(
         scene, state, _C.SetGrads(**g), timed, _C.SetTimedGrads(dL_dmeans3D_v=a, dL_dscales_v=a), None))
     assert b"null pointer argument" in err(lib.gsr_set_timed_preprocess(scene, state, None, None))
+
+
+def test_null_background_is_rejected_before_any_device_work():
+    """A NULL entry of the bgs table fails the validation of gsr_set_render and gsr_set_backward: with no GPU here,
+    a call that reached HIP first would report a HIP failure (2) instead."""
+    lib = _C.load_library()
+    null_bg = (ctypes.c_void_p * 1)(None)
+    a, scene, state = _structs(means3D=16, bgs=null_bg)
+    out = _C.SetOutputs(out_color=a, out_depth=a, out_alpha=a)
+    assert lib.gsr_set_render(scene, state, out, None) == 1
+    assert b"null background" in lib.gsr_last_error()
+    g = _C.SetGrads(dL_dcolor=a, dL_dmeans2D=a, dL_dcolors=a, dL_dopacity=a, dL_dmeans3D=a, dL_dscales=a,
+                    dL_drotations=a, work=a, work_bytes=1 << 30)
+    assert lib.gsr_set_backward(scene, state, g, None) == 1
+    assert b"null background" in lib.gsr_last_error()
+
+
+class _StubLib:
+    """Stands in for the library under the Python drivers: records the calls' names; sizes are 64 bytes, every view
+    renders one instance, everything else succeeds."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        def call(*args):
+            self.calls.append(name)
+            if name == "gsr_set_num_rendered":
+                for v in range(args[0]):
+                    args[3][v] = 1
+            return 64 if name.endswith("_bytes") else 0
+        return call
+
+
+def test_plain_and_timed_forwards_share_one_driver(monkeypatch):
+    """Without a device: the forwards of rasterize_views and rasterize_timed_views (V = 3, sets of 2) record the same
+    host phases and issue the same library calls in the same order, but for the preprocess entry."""
+    V, P = 3, 7
+    s = [rf.GaussianRasterizationSettings(H, W, 0.5, 0.5, torch.zeros(3), 1.0, torch.eye(4), torch.eye(4), 0,
+                                          torch.zeros(3), False, False) for _ in range(V)]
+    monkeypatch.setattr(_C, "HOST_TRACE", True)
+    monkeypatch.setattr(_C, "_require_gpu", lambda dev: None)
+    monkeypatch.setattr(_C, "_stream", lambda dev: None)
+    monkeypatch.setattr(_C, "_f32", lambda t, name, dev: None if t is None or t.numel() == 0 else t.contiguous())
+    monkeypatch.setattr(batched, "SET_MAX", 2)
+    ctx = types.SimpleNamespace(save_for_backward=lambda *t: None, mark_non_differentiable=lambda *t: None)
+    m2 = [torch.zeros(P, 3) for _ in range(V)]
+    op, col, sc, rot = torch.zeros(P, 1), torch.zeros(P, 3), torch.zeros(P, 3), torch.zeros(P, 4)
+    runs = {}
+    for name in ("plain", "timed"):
+        lib = _StubLib()
+        monkeypatch.setattr(_C, "load_library", lambda lib=lib: lib)
+        _C.host_trace_read(reset=True)
+        if name == "plain":
+            out = batched._RasterizeViews.forward(ctx, s, None, "fused", False, torch.zeros(P, 3), None, col, op, sc,
+                                                  rot, None, None, None, *m2)
+        else:
+            out = batched._RasterizeTimedViews.forward(ctx, s, False, torch.zeros(V, P, 3), col, op, sc, rot, None,
+                                                       None, *m2)
+        assert [tuple(t.shape) for t in out] == [(V, 3, H, W), (V, P), (V, 1, H, W), (V, 1, H, W)]
+        assert [(vs.lo, vs.hi, vs.K) for vs in ctx.sets] == [(0, 2, [1, 1]), (2, 3, [1])]
+        runs[name] = (set(_C.host_trace_read(reset=True)), lib.calls)
+    _C.host_trace_read(reset=True)
+    assert runs["plain"][0] == runs["timed"][0] == {"fwd_setup", "fwd_preprocess_launch", "fwd_sync_wait",
+                                                    "fwd_render_launch"}
+    assert "gsr_set_timed_preprocess" in runs["timed"][1] and runs["plain"][1].count("gsr_set_preprocess") == 2
+    assert [c.replace("gsr_set_timed_preprocess", "gsr_set_preprocess") for c in runs["timed"][1]] == runs["plain"][1]
+    # both preprocesses are enqueued before the first host sync
+    assert runs["plain"][1].index("gsr_set_num_rendered") > max(
+        i for i, c in enumerate(runs["plain"][1]) if c == "gsr_set_preprocess")
 
 
 def test_rasterize_timed_views_checks_shapes_before_device_work():

@@ -184,6 +184,25 @@ static int check_set(int V, int P) {
   return GSR_OK;
 }
 
+// What the forward and the backward blend of a set derive alike from its carved state.  The callers set the rest: the
+// composite and second-colour pointers, ckpt, ochunk, qbytes, V / v0 and the per-view tables.
+static void render_set_shared(RenderSet& rs, const GeomState& g, const ImageState& img, const BinningState& b,
+                              const TilePack& tp, int tres, int V, int P, int width, int height) {
+  rs.P = P;
+  rs.W = width;
+  rs.H = height;
+  rs.gx = div_up(width, GSR_TILE_X);
+  rs.gy = div_up(height, GSR_TILE_Y);
+  rs.gmask = tp.gmask;
+  rs.col2_rec = g.drange + 130;
+  rs.order = img.order;
+  rs.split_mode = img.split_mode;
+  rs.split_items = img.split_items;
+  rs.split_cap = img.split_cap;
+  rs.split_extra = split_extra(V, (size_t)rs.gx * rs.gy);
+  rs.qkeys = tp.qmask ? b.key[tres] : nullptr;
+}
+
 extern "C" {
 
 #ifndef GSR_BUILD_ID
@@ -1147,6 +1166,8 @@ int gsr_set_render(const gsr_set_scene* scene, const gsr_set_state* state, const
   if (K == nullptr || bgs == nullptr || geom == nullptr || binning == nullptr || image == nullptr ||
       o.out_color == nullptr || o.out_depth == nullptr || o.out_alpha == nullptr)
     return fail(GSR_EINVAL, "%s", "null pointer argument");
+  for (int v = 0; v < V; ++v)
+    if (bgs[v] == nullptr) return fail(GSR_EINVAL, "%s", "null background");
   SegInfo inst;
   long long total = 0;
   if (inst_segments(V, K, inst, &total) != GSR_OK) return GSR_EINVAL;
@@ -1180,33 +1201,20 @@ int gsr_set_render(const gsr_set_scene* scene, const gsr_set_state* state, const
   {
     PhaseScope ps(GSR_PHASE_RENDER_FWD, s);
     RenderSet rs;
+    render_set_shared(rs, g, img, b, tp, tres, V, P, width, height);
     rs.cbg = o.bg_images;
     rs.comp = o.out_render;
     rs.ccolor = nullptr;
     rs.dcbg = nullptr;
     rs.col2 = colors2;
-    rs.col2_rec = g.drange + 130;
     rs.out_col2 = o.out_color2;
     rs.dpix2 = nullptr;
-    rs.order = img.order;
     rs.ochunk = order_chunk(V, gx, gy, true);
     rs.ckpt = split ? img.ckpt : nullptr;
-    rs.split_mode = img.split_mode;
-    rs.split_items = img.split_items;
-    rs.split_cap = img.split_cap;
-    rs.split_extra = split_extra(V, (size_t)gx * gy);
-    rs.qkeys = tp.qmask ? b.key[tres] : nullptr;
     rs.qbytes = total > 0 ? reinterpret_cast<uint8_t*>(b.key[tres ^ 1]) : nullptr;
     rs.V = V;
     rs.v0 = 0;
-    rs.P = P;
-    rs.W = width;
-    rs.H = height;
-    rs.gx = gx;
-    rs.gy = gy;
-    rs.gmask = tp.gmask;
     for (int v = 0; v < V; ++v) {
-      if (bgs[v] == nullptr) return fail(GSR_EINVAL, "%s", "null background");
       rs.inst_start[v] = inst.start[v];
       rs.row_start[v] = 0;
       rs.bg[v] = bgs[v];
@@ -1257,6 +1265,8 @@ static int set_backward(const gsr_set_scene* scene, const gsr_set_state* state, 
       gr.dL_dcolors == nullptr || gr.dL_dopacity == nullptr || (timed == nullptr && gr.dL_dmeans3D == nullptr) ||
       state->radii == nullptr || sc.means3D == nullptr)
     return fail(GSR_EINVAL, "%s", "null pointer argument");
+  for (int v = 0; v < V; ++v)
+    if (bgs[v] == nullptr) return fail(GSR_EINVAL, "%s", "null background");
   if (sc.shs != nullptr && gr.dL_dsh == nullptr) return fail(GSR_EINVAL, "%s", "dL_dsh required with SHs");
   // (a timed set's per-view scales / rotations have per-view gradients: gsr_set_timed_backward checked those)
   const bool need_dscales = timed == nullptr || timed->scales_v == nullptr;
@@ -1300,35 +1310,23 @@ static int set_backward(const gsr_set_scene* scene, const gsr_set_state* state, 
       return fail(GSR_EINVAL, "%s", "backward work buffer smaller than one view's gradient rows");
     BackwardState bw = BackwardState::carve(work, rows, P, two);
     RenderSet rs;
+    render_set_shared(rs, g, img, b, tp, tres, V, P, width, height);
     rs.cbg = comp_bg ? comp_bg + (size_t)g0 * HW * 3 : nullptr;
     rs.comp = nullptr;
     rs.ccolor = color ? color + (size_t)g0 * 3 * HW : nullptr;
     rs.dcbg = dL_dbg ? dL_dbg + (size_t)g0 * HW * 3 : nullptr;
     rs.col2 = two ? gr.colors2 : colors_override;
-    rs.col2_rec = g.drange + 130;
     rs.out_col2 = nullptr;
     rs.dpix2 = two ? gr.dL_dcolor2 + (size_t)g0 * 3 * HW : nullptr;
-    rs.order = img.order;
     // a one-colour backward of the first colour replays split chunks when the forward wrote them.  The host passes
     // the checkpoints whenever the set's size allows a split (split_fits, no environment read here: ADVICE r05) and
     // the kernels follow the decision the forward recorded on the device (split_mode): the extra workgroups of a
     // forward that did not split return at once, and the checkpoints are read only after one that did
     rs.ckpt = !two && colors_override == nullptr && split_fits(V, (size_t)gx * gy) ? img.ckpt : nullptr;
-    rs.split_mode = img.split_mode;
-    rs.split_items = img.split_items;
-    rs.split_cap = img.split_cap;
-    rs.split_extra = split_extra(V, (size_t)gx * gy);
-    rs.qkeys = tp.qmask ? b.key[tres] : nullptr;
     rs.qbytes = reinterpret_cast<uint8_t*>(b.key[tres ^ 1]);  // (valid when img.split_mode[1] says so)
     rs.V = g1 - g0;
     rs.ochunk = order_chunk(rs.V, gx, gy, false);
     rs.v0 = g0;
-    rs.P = P;
-    rs.W = width;
-    rs.H = height;
-    rs.gx = gx;
-    rs.gy = gy;
-    rs.gmask = tp.gmask;
     ViewGradArgs va;
     va.V = g1 - g0;
     va.v0 = g0;
@@ -1354,7 +1352,6 @@ static int set_backward(const gsr_set_scene* scene, const gsr_set_state* state, 
     ab.dcov_carry = carry;
     ab.dcolors2 = two ? gr.dL_dcolors2 : nullptr;
     for (int v = g0; v < g1; ++v) {
-      if (bgs[v] == nullptr) return fail(GSR_EINVAL, "%s", "null background");
       rs.inst_start[v - g0] = inst.start[v];
       rs.row_start[v - g0] = inst.start[v] - inst.start[g0];
       rs.bg[v - g0] = bgs[v];

@@ -17,6 +17,7 @@ import ctypes
 import math
 import os
 import time
+import types
 
 import torch
 
@@ -69,6 +70,127 @@ class _ViewSet:
             setattr(self.state, name, _addr(t))
 
 
+def _view_set(lo, settings, gaussians, radii):
+    """The _ViewSet of views lo .. lo + len(settings) of a batch: their cameras, the Gaussians' arrays and their rows
+    of radii (the sizes and flags the views of a batch share are read from the first)."""
+    s0, dev = settings[0], radii.device
+    f = lambda t, n: _C._f32(t, n, dev)  # noqa: E731
+    cams = [(f(s.viewmatrix, "viewmatrix"), f(s.projmatrix, "projmatrix"), f(s.campos, "campos"), f(s.bg, "bg"))
+            for s in settings]
+    return _ViewSet(lo, lo + len(settings), cams, [float(s.tanfovx) for s in settings],
+                    [float(s.tanfovy) for s in settings], gaussians, radii, P=int(radii.shape[1]),
+                    degree=int(s0.sh_degree), M=_C.sh_coeff_count(gaussians["shs"]), width=int(s0.image_width),
+                    height=int(s0.image_height), prefiltered=int(bool(s0.prefiltered)),
+                    scale_modifier=float(s0.scale_modifier))
+
+
+def _forward_sets(settings_list, gaussians, P, dev, composite_bg, clamp, preprocess, colors2_of=None):
+    """The forward of a batch as view sets.  preprocess(vs, stream) enqueues a set's preprocess; colors2_of(vs) is the
+    set's second colours (None: one colour).  Every preprocess is enqueued before the first host sync.  Returns the
+    sets and the output tensors."""
+    t0 = time.perf_counter()
+    lib = _C.load_library()
+    V = len(settings_list)
+    H, W = int(settings_list[0].image_height), int(settings_list[0].image_width)
+    stream = _C._stream(dev)
+    fopt = dict(dtype=torch.float32, device=dev)
+    color = torch.empty((V, 3, H, W), **fopt)
+    cbg = None
+    # the renderer's clamp(0, 1) fused into the blends without a background image (clamp_only) or with it
+    clamp_only = bool(clamp) and composite_bg is None
+    if composite_bg is not None:
+        cbg = _C._f32(composite_bg, "background", dev).reshape(V, H, W, 3)
+    fused_out = cbg is not None or clamp_only
+    render = torch.empty((V, 3, H, W), **fopt) if fused_out else None
+    depth = torch.empty((V, 1, H, W), **fopt)
+    alpha = torch.empty((V, 1, H, W), **fopt)
+    color2 = torch.empty((V, 3, H, W), **fopt) if colors2_of is not None else None
+    radii = torch.empty((V, P), dtype=torch.int32, device=dev)
+    sets = []
+    for lo in range(0, V, SET_MAX):
+        vs = _view_set(lo, settings_list[lo:lo + SET_MAX], gaussians, radii[lo:lo + SET_MAX])
+        vs.allocate(geom=torch.empty(int(lib.gsr_set_geom_bytes(vs.V, P)), dtype=torch.uint8, device=dev))
+        t0 = _C.host_mark("fwd_setup", t0)
+        preprocess(vs, stream)
+        sets.append(vs)
+        t0 = _C.host_mark("fwd_preprocess_launch", t0)
+    for vs in sets:
+        K = (ctypes.c_int * vs.V)()
+        L = (ctypes.c_int * vs.V)()
+        # the reference's one host sync: the instance counts size the binning buffers
+        _C._check(lib.gsr_set_num_rendered(vs.V, _C._ptr(vs.geom), P, K, None, L, stream))
+        t0 = _C.host_mark("fwd_sync_wait", t0)
+        vs.K = list(K)
+        _C.RECENT_LISTED.extend(L)
+        _C.RECENT_FORWARDS.extend((k, H, W) for k in vs.K)
+        vs.state.num_rendered = K
+        vs.allocate(
+            binning=torch.empty(int(lib.gsr_set_binning_bytes(vs.V, P, K, W, H)), dtype=torch.uint8, device=dev),
+            image=torch.empty(int(lib.gsr_set_image_bytes(vs.V, P, K, W, H, int(colors2_of is not None))),
+                              dtype=torch.uint8, device=dev))
+        sl = slice(vs.lo, vs.hi)
+        out = _C.SetOutputs(out_color=_addr(color[sl]), out_depth=_addr(depth[sl]), out_alpha=_addr(alpha[sl]))
+        if cbg is not None:
+            out.bg_images = _addr(cbg[sl])
+        if fused_out:
+            out.out_render = _addr(render[sl])
+        if colors2_of is not None:
+            out.colors2, out.out_color2 = _addr(colors2_of(vs)), _addr(color2[sl])
+        _C._check(lib.gsr_set_render(vs.scene, vs.state, out, stream))
+        t0 = _C.host_mark("fwd_render_launch", t0)
+    return types.SimpleNamespace(sets=sets, color=color, render=render, depth=depth, alpha=alpha, color2=color2,
+                                 radii=radii, cbg=cbg)
+
+
+def _outputs(r):
+    """(render if the forward fused a clamp or composite else color, radii, depth, alpha[, color2])."""
+    first = r.color if r.render is None else r.render
+    return (first, r.radii, r.depth, r.alpha) if r.color2 is None else (first, r.radii, r.depth, r.alpha, r.color2)
+
+
+def _set_work(lib, vs, two):
+    """The backward's work buffer for a set: all its views' gradient rows when WORK_BUDGET allows, one view's at the
+    least (the scratch grows with K: the largest single view bounds what a view group needs)."""
+    P = vs.scene.P
+    kmax = _arr(ctypes.c_int, [max(vs.K)])
+    need = int(lib.gsr_set_backward_bytes(vs.V, P, vs.state.num_rendered, int(two)))
+    largest = int(lib.gsr_set_backward_bytes(1, P, kmax, int(two)))
+    return torch.empty(max(largest, min(need, WORK_BUDGET)), dtype=torch.uint8, device=vs.geom.device)
+
+
+def _upstream(g):
+    return g.float().contiguous() if g is not None else None
+
+
+def _set_grads(g, vs, rows, work, accumulate):
+    """Point the per-set fields of a SetGrads at the set's views: rows maps a field to its (V, ...) tensor or None."""
+    for name, t in rows.items():
+        setattr(g, name, _addr(t[vs.lo:vs.hi]) if t is not None else None)
+    g.accumulate = int(accumulate)
+    g.work, g.work_bytes = _addr(work), work.numel()
+
+
+def _masked_grads(ctx, grads, bg_at):
+    """The backward's gradient list with dL/dbackground (at bg_at) in the caller's shape and None where no gradient is
+    needed."""
+    if grads[bg_at] is not None:
+        grads[bg_at] = grads[bg_at].reshape(ctx.bg_shape)
+    return [g if need else None for g, need in zip(grads, ctx.needs_input_grad)]
+
+
+def _check_views(settings_list, background, size_error):
+    """The rules every view of a batch obeys (size_error: what a mismatch of image sizes raises)."""
+    s0 = settings_list[0]
+    H, W = int(s0.image_height), int(s0.image_width)
+    if any(int(s.image_height) != H or int(s.image_width) != W for s in settings_list):
+        raise size_error("all views of a batch must have the same image size")
+    if any(int(s.sh_degree) != int(s0.sh_degree) or float(s.scale_modifier) != float(s0.scale_modifier)
+           or bool(s.prefiltered) != bool(s0.prefiltered) for s in settings_list):
+        raise ValueError("sh_degree, scale_modifier and prefiltered must be shared by the views of a batch")
+    if background is not None and background.numel() != len(settings_list) * H * W * 3:
+        raise ValueError("background must hold (V, H, W, 3) values")
+
+
 # A two-colour forward hands colors2 to the preprocess too (gsr_set_preprocess), which writes each Gaussian's
 # second colour into the record it writes anyway; the blends then read it from the record's line.  False: the
 # blends gather colors2 apart (the same bits; tests/test_gpu_configs.py compares the two).
@@ -81,95 +203,39 @@ class _RasterizeViews(torch.autograd.Function):
                 rotations, cov3D_precomp, composite_bg, colors2, *means2D):
         t0 = time.perf_counter()
         lib = _C.load_library()
-        V = len(settings_list)
         dev = means3D.device
         _C._require_gpu(dev)
         P = int(means3D.shape[0])
-        s0 = settings_list[0]
-        H, W = int(s0.image_height), int(s0.image_width)
-        if any(int(s.image_height) != H or int(s.image_width) != W for s in settings_list):
-            raise _C.GSRError("all views of a batch must have the same image size")
         f = lambda t, n: _C._f32(t, n, dev)  # noqa: E731
         m3, shc, col, op, sc, rot, c3 = (f(means3D, "means3D"), f(sh, "sh"), f(colors_precomp, "colors_precomp"),
                                          f(opacities, "opacities"), f(scales, "scales"), f(rotations, "rotations"),
                                          f(cov3D_precomp, "cov3D_precomp"))
         if (shc is None) == (col is None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
-        M = _C.sh_coeff_count(shc)
-        p = _C._ptr
-        stream = _C._stream(dev)
-        fopt = dict(dtype=torch.float32, device=dev)
-        color = torch.empty((V, 3, H, W), **fopt)
-        cbg = None
-        # the renderer's clamp(0, 1) fused into the blends without a background image (clamp_only) or with it
-        clamp_only = bool(clamp) and composite_bg is None
-        if composite_bg is not None:
-            cbg = _C._f32(composite_bg, "background", dev).reshape(V, H, W, 3)
-        fused_out = cbg is not None or clamp_only
-        if fused_out:
-            render = torch.empty((V, 3, H, W), **fopt)
-        depth = torch.empty((V, 1, H, W), **fopt)
-        alpha = torch.empty((V, 1, H, W), **fopt)
         c2 = None
         if colors2 is not None:
-            c2 = _C._f32(colors2, "colors2", dev)
+            c2 = f(colors2, "colors2")
             if c2.numel() != 3 * P:
                 raise _C.GSRError(f"colors2 has {c2.numel()} elements, expected {3 * P}")
-            color2 = torch.empty((V, 3, H, W), **fopt)
-        radii = torch.empty((V, P), dtype=torch.int32, device=dev)
-        sets = []
         gaussians = dict(means3D=m3, scales=sc, rotations=rot, opacities=op, shs=shc, colors_precomp=col,
                          cov3D_precomp=c3)
-        for lo in range(0, V, SET_MAX):
-            hi = min(V, lo + SET_MAX)
-            cams = [(f(s.viewmatrix, "viewmatrix"), f(s.projmatrix, "projmatrix"), f(s.campos, "campos"),
-                     f(s.bg, "bg")) for s in settings_list[lo:hi]]
-            vs = _ViewSet(lo, hi, cams, [float(s.tanfovx) for s in settings_list[lo:hi]],
-                          [float(s.tanfovy) for s in settings_list[lo:hi]], gaussians, radii[lo:hi], P=P,
-                          degree=int(s0.sh_degree), M=M, width=W, height=H, prefiltered=int(bool(s0.prefiltered)),
-                          scale_modifier=float(s0.scale_modifier))
-            vs.allocate(geom=torch.empty(int(lib.gsr_set_geom_bytes(vs.V, P)), dtype=torch.uint8, device=dev))
-            t0 = _C.host_mark("fwd_setup", t0)
-            # (the second colour set, when there is one, rides in the records the preprocess writes: the two-colour
-            # blends then read it with the record instead of gathering it apart)
-            _C._check(lib.gsr_set_preprocess(vs.scene, vs.state, p(c2) if c2 is not None and EMBED_COLORS2 else None,
-                                             stream))
-            sets.append(vs)
-            t0 = _C.host_mark("fwd_preprocess_launch", t0)
-        for vs in sets:
-            K = (ctypes.c_int * vs.V)()
-            L = (ctypes.c_int * vs.V)()
-            # the reference's one host sync: the instance counts size the binning buffers
-            _C._check(lib.gsr_set_num_rendered(vs.V, p(vs.geom), P, K, None, L, stream))
-            t0 = _C.host_mark("fwd_sync_wait", t0)
-            vs.K = list(K)
-            _C.RECENT_LISTED.extend(L)
-            _C.RECENT_FORWARDS.extend((k, H, W) for k in vs.K)
-            vs.state.num_rendered = K
-            vs.allocate(
-                binning=torch.empty(int(lib.gsr_set_binning_bytes(vs.V, P, K, W, H)), dtype=torch.uint8, device=dev),
-                image=torch.empty(int(lib.gsr_set_image_bytes(vs.V, P, K, W, H, int(c2 is not None))),
-                                  dtype=torch.uint8, device=dev))
-            sl = slice(vs.lo, vs.hi)
-            out = _C.SetOutputs(out_color=_addr(color[sl]), out_depth=_addr(depth[sl]), out_alpha=_addr(alpha[sl]))
-            if cbg is not None:
-                out.bg_images = _addr(cbg[sl])
-            if fused_out:
-                out.out_render = _addr(render[sl])
-            if c2 is not None:
-                out.colors2, out.out_color2 = _addr(c2), _addr(color2[sl])
-            _C._check(lib.gsr_set_render(vs.scene, vs.state, out, stream))
-            t0 = _C.host_mark("fwd_render_launch", t0)
+
+        # (the second colour set, when there is one, rides in the records the preprocess writes: the two-colour
+        # blends then read it with the record instead of gathering it apart)
+        def preprocess(vs, stream):
+            _C._check(lib.gsr_set_preprocess(vs.scene, vs.state, _C._ptr(c2) if EMBED_COLORS2 else None, stream))
+
+        _C.host_mark("fwd_setup", t0)
+        r = _forward_sets(settings_list, gaussians, P, dev, composite_bg, clamp, preprocess,
+                          (lambda vs: c2) if c2 is not None else None)
         ctx.settings = settings_list
         ctx.grad_reduce = grad_reduce
         ctx.two_color_bwd = two_color_bwd
-        ctx.sets = sets
+        ctx.sets = r.sets
         ctx.bg_shape = tuple(composite_bg.shape) if composite_bg is not None else None
-        ctx.save_for_backward(m3, shc, col, sc, rot, c3, radii, cbg, color if fused_out else None, c2)
-        ctx.mark_non_differentiable(radii)
-        if c2 is not None:
-            return (render if fused_out else color), radii, depth, alpha, color2
-        return (render if fused_out else color), radii, depth, alpha
+        ctx.save_for_backward(m3, shc, col, sc, rot, c3, r.radii, r.cbg, r.color if r.render is not None else None, c2)
+        ctx.mark_non_differentiable(r.radii)
+        return _outputs(r)
 
     @staticmethod
     def backward(ctx, g_color, _g_radii, g_depth, g_alpha, g_color2=None):
@@ -177,13 +243,10 @@ class _RasterizeViews(torch.autograd.Function):
         lib = _C.load_library()
         m3, shc, col, sc, rot, c3, radii, cbg, color, c2 = ctx.saved_tensors
         second = c2 is not None and g_color2 is not None
-        settings = ctx.settings
-        V = len(settings)
-        s0 = settings[0]
+        V = len(ctx.settings)
         dev = m3.device
         P = int(m3.shape[0])
         M = _C.sh_coeff_count(shc)
-        H, W = int(s0.image_height), int(s0.image_width)
         fopt = dict(dtype=torch.float32, device=dev)
         d_m2 = torch.empty((V, P, 3), **fopt)
         # the per-Gaussian gradients are carved from one buffer (means3D, scales, rotations, opacities,
@@ -216,15 +279,14 @@ class _RasterizeViews(torch.autograd.Function):
                 if t is not None:
                     t.zero_()
         else:
-            gc = g_color.float().contiguous()
-            gd = g_depth.float().contiguous() if g_depth is not None else None
-            ga = g_alpha.float().contiguous() if g_alpha is not None else None
             stream = _C._stream(dev)
             # both calls of a two-colour forward in one backward pass (the colors2 fields of gsr_set_grads);
             # two_color_backward="separate" runs the second call's backward after the first's instead
             fused2 = second and ctx.two_color_bwd != "separate"
-            if second:
-                g2 = g_color2.float().contiguous()
+            g2 = _upstream(g_color2) if second else None
+            # (a forward with a fused clamp or composite: dL_dcolor is dL/drender, masked by the forward's colour)
+            rows = dict(dL_dcolor=_upstream(g_color), dL_ddepth=_upstream(g_depth), dL_dalpha=_upstream(g_alpha),
+                        color=color, bg_images=cbg, dL_dbg=d_bg, dL_dmeans2D=d_m2, dL_dcolor2=g2 if fused2 else None)
             reducer = ctx.grad_reduce if ctx.grad_reduce is not None and ctx.grad_reduce.active() else None
             # per-range events only when the last set's call is the last writer of the per-Gaussian sums: with
             # the second colour's backward run separately after it (two_color_backward="separate"), that call
@@ -240,23 +302,8 @@ class _RasterizeViews(torch.autograd.Function):
                 if events is not None and si == len(ctx.sets) - 1:
                     # the last set's call forms the final per-Gaussian sums: in ranges, an event after each
                     g.n_chunks, g.chunk_events = len(events), _arr(ctypes.c_void_p, [e.cuda_event for e in events])
-                # (the scratch grows with K: the largest single view bounds what a view group needs)
-                kmax = _arr(ctypes.c_int, [max(vs.K)])
-                need = int(lib.gsr_set_backward_bytes(vs.V, P, vs.state.num_rendered, int(fused2)))
-                largest = int(lib.gsr_set_backward_bytes(1, P, kmax, int(fused2)))
-                work = torch.empty(max(largest, min(need, WORK_BUDGET)), dtype=torch.uint8, device=dev)
-                sl = slice(vs.lo, vs.hi)
-                g.dL_dcolor, g.dL_dmeans2D = _addr(gc[sl]), _addr(d_m2[sl])
-                g.dL_ddepth = _addr(gd[sl]) if gd is not None else None
-                g.dL_dalpha = _addr(ga[sl]) if ga is not None else None
-                # (a forward with a fused clamp or composite: gc is dL/drender, masked by the forward's colour)
-                g.color = _addr(color[sl]) if color is not None else None
-                g.bg_images = _addr(cbg[sl]) if cbg is not None else None
-                g.dL_dbg = _addr(d_bg[sl]) if d_bg is not None else None
-                if fused2:
-                    g.dL_dcolor2 = _addr(g2[sl])
-                g.accumulate = 1 if si > 0 else 0
-                g.work, g.work_bytes = _addr(work), work.numel()
+                work = _set_work(lib, vs, fused2)
+                _set_grads(g, vs, rows, work, accumulate=si > 0)
                 _C._check(lib.gsr_set_backward(vs.scene, vs.state, g, stream))
                 if second and not fused2:
                     # the second call's backward on the shared forward state: precomputed colours, so a scene
@@ -266,18 +313,13 @@ class _RasterizeViews(torch.autograd.Function):
                     scene2.shs = None
                     m2_scratch = torch.empty((vs.V, P, 3), **fopt)
                     _C._check(lib.gsr_set_backward(scene2, vs.state, _C.SetGrads(
-                        colors_override=_addr(c2), dL_dcolor=_addr(g2[sl]), dL_dmeans2D=_addr(m2_scratch),
+                        colors_override=_addr(c2), dL_dcolor=_addr(g2[vs.lo:vs.hi]), dL_dmeans2D=_addr(m2_scratch),
                         dL_dcolors=_addr(d_c2), accumulate=1, work=_addr(work), work_bytes=work.numel(), **shared),
                         stream))
-        if d_bg is not None:
-            d_bg = d_bg.reshape(ctx.bg_shape)
         if getattr(ctx, "needs_c3_scratch", False):
             d_c3 = None
-        grads = [None, None, None, None, d_m3, d_sh, d_col, d_op, d_sc, d_rot, d_c3, d_bg, d_c2] + \
-            [d_m2[v] for v in range(V)]
-        for k, need in enumerate(ctx.needs_input_grad):
-            if not need:
-                grads[k] = None
+        grads = _masked_grads(ctx, [None, None, None, None, d_m3, d_sh, d_col, d_op, d_sc, d_rot, d_c3, d_bg, d_c2]
+                              + [d_m2[v] for v in range(V)], bg_at=11)
         if ctx.grad_reduce is not None and P > 0:
             # the per-Gaussian gradients' sums over ranks, range by range as the backward finishes them
             shared = [grads[k] for k in (4, 5, 6, 7, 8, 9, 10, 12)]
@@ -327,14 +369,7 @@ def rasterize_views(settings_list, means3D, means2D_list, opacities, shs=None, c
         raise ValueError("one means2D placeholder per view")
     if not settings_list:
         raise ValueError("at least one view")
-    s0 = settings_list[0]
-    if any(int(s.sh_degree) != int(s0.sh_degree) or float(s.scale_modifier) != float(s0.scale_modifier)
-           or bool(s.prefiltered) != bool(s0.prefiltered) for s in settings_list):
-        raise ValueError("sh_degree, scale_modifier and prefiltered must be shared by the views of a batch")
-    if background is not None:
-        H, W = int(s0.image_height), int(s0.image_width)
-        if background.numel() != len(settings_list) * H * W * 3:
-            raise ValueError("background must hold (V, H, W, 3) values")
+    _check_views(settings_list, background, size_error=_C.GSRError)
     if two_color_backward not in ("fused", "separate"):
         raise ValueError("two_color_backward is 'fused' or 'separate'")
     return _RasterizeViews.apply(list(settings_list), grad_reduce, two_color_backward, bool(clamp), means3D, shs,
@@ -348,83 +383,39 @@ class _RasterizeTimedViews(torch.autograd.Function):
     @staticmethod
     def forward(ctx, settings_list, clamp, means3D, colors_precomp, opacities, scales, rotations, composite_bg, colors2,
                 *means2D):
+        t0 = time.perf_counter()
         lib = _C.load_library()
-        V = len(settings_list)
         dev = means3D.device
         P = int(means3D.shape[1])
-        s0 = settings_list[0]
-        H, W = int(s0.image_height), int(s0.image_width)
-        f = lambda t, n: _C._f32(t, n, dev)  # noqa: E731
         keep = lambda t: t.detach().contiguous()  # noqa: E731  (fp32 on `dev`: rasterize_timed_views checked)
         m3, col, op, sc, rot = keep(means3D), keep(colors_precomp), keep(opacities), keep(scales), keep(rotations)
         c2 = keep(colors2) if colors2 is not None else None
         sc_v, rot_v, c2_v = sc.dim() == 3, rot.dim() == 3, c2 is not None and c2.dim() == 3
-        p = _C._ptr
-        stream = _C._stream(dev)
-        fopt = dict(dtype=torch.float32, device=dev)
-        color = torch.empty((V, 3, H, W), **fopt)
-        cbg = None
-        clamp_only = bool(clamp) and composite_bg is None
-        if composite_bg is not None:
-            cbg = _C._f32(composite_bg, "background", dev).reshape(V, H, W, 3)
-        fused_out = cbg is not None or clamp_only
-        render = torch.empty((V, 3, H, W), **fopt) if fused_out else None
-        depth = torch.empty((V, 1, H, W), **fopt)
-        alpha = torch.empty((V, 1, H, W), **fopt)
-        color2 = torch.empty((V, 3, H, W), **fopt) if c2 is not None else None
-        radii = torch.empty((V, P), dtype=torch.int32, device=dev)
-        sets = []
         # what the views share goes into the scene; the per-view arrays into the set's gsr_set_timed
         gaussians = dict(means3D=None, scales=None if sc_v else sc, rotations=None if rot_v else rot, opacities=op,
                          shs=None, colors_precomp=col, cov3D_precomp=None)
-        for lo in range(0, V, SET_MAX):
-            hi = min(V, lo + SET_MAX)
-            cams = [(f(s.viewmatrix, "viewmatrix"), f(s.projmatrix, "projmatrix"), f(s.campos, "campos"),
-                     f(s.bg, "bg")) for s in settings_list[lo:hi]]
-            vs = _ViewSet(lo, hi, cams, [float(s.tanfovx) for s in settings_list[lo:hi]],
-                          [float(s.tanfovy) for s in settings_list[lo:hi]], gaussians, radii[lo:hi], P=P,
-                          degree=int(s0.sh_degree), M=0, width=W, height=H, prefiltered=int(bool(s0.prefiltered)),
-                          scale_modifier=float(s0.scale_modifier))
-            vs.timed = _C.SetTimed(means3D_v=_addr(m3[lo:hi]), scales_v=_addr(sc[lo:hi]) if sc_v else None,
-                                   rotations_v=_addr(rot[lo:hi]) if rot_v else None,
-                                   colors2_v=_addr(c2[lo:hi]) if c2_v else None)
-            vs.allocate(geom=torch.empty(int(lib.gsr_set_geom_bytes(vs.V, P)), dtype=torch.uint8, device=dev))
-            _C._check(lib.gsr_set_timed_preprocess(vs.scene, vs.state, vs.timed, stream))
-            sets.append(vs)
-        for vs in sets:
-            K = (ctypes.c_int * vs.V)()
-            L = (ctypes.c_int * vs.V)()
-            # the one host sync of the set: the instance counts size the binning buffers
-            _C._check(lib.gsr_set_num_rendered(vs.V, p(vs.geom), P, K, None, L, stream))
-            vs.K = list(K)
-            _C.RECENT_LISTED.extend(L)
-            _C.RECENT_FORWARDS.extend((k, H, W) for k in vs.K)
-            vs.state.num_rendered = K
-            vs.allocate(
-                binning=torch.empty(int(lib.gsr_set_binning_bytes(vs.V, P, K, W, H)), dtype=torch.uint8, device=dev),
-                image=torch.empty(int(lib.gsr_set_image_bytes(vs.V, P, K, W, H, int(c2 is not None))),
-                                  dtype=torch.uint8, device=dev))
+
+        def preprocess(vs, stream):
             sl = slice(vs.lo, vs.hi)
-            out = _C.SetOutputs(out_color=_addr(color[sl]), out_depth=_addr(depth[sl]), out_alpha=_addr(alpha[sl]))
-            if cbg is not None:
-                out.bg_images = _addr(cbg[sl])
-            if fused_out:
-                out.out_render = _addr(render[sl])
-            if c2 is not None:
-                # per view: the pointer the preprocess embedded (the blends read the records); shared: gathered
-                out.colors2, out.out_color2 = _addr(c2[sl]) if c2_v else _addr(c2), _addr(color2[sl])
-            _C._check(lib.gsr_set_render(vs.scene, vs.state, out, stream))
+            vs.timed = _C.SetTimed(means3D_v=_addr(m3[sl]), scales_v=_addr(sc[sl]) if sc_v else None,
+                                   rotations_v=_addr(rot[sl]) if rot_v else None,
+                                   colors2_v=_addr(c2[sl]) if c2_v else None)
+            _C._check(lib.gsr_set_timed_preprocess(vs.scene, vs.state, vs.timed, stream))
+
+        _C.host_mark("fwd_setup", t0)
+        # (second colours per view: the pointer the preprocess embedded, the blends read the records; shared: gathered)
+        r = _forward_sets(settings_list, gaussians, P, dev, composite_bg, clamp, preprocess,
+                          (lambda vs: c2[vs.lo:vs.hi] if c2_v else c2) if c2 is not None else None)
         ctx.settings = settings_list
-        ctx.sets = sets
+        ctx.sets = r.sets
         ctx.bg_shape = tuple(composite_bg.shape) if composite_bg is not None else None
-        ctx.save_for_backward(m3, col, sc, rot, radii, cbg, color if fused_out else None, c2)
-        ctx.mark_non_differentiable(radii)
-        if c2 is not None:
-            return (render if fused_out else color), radii, depth, alpha, color2
-        return (render if fused_out else color), radii, depth, alpha
+        ctx.save_for_backward(m3, col, sc, rot, r.radii, r.cbg, r.color if r.render is not None else None, c2)
+        ctx.mark_non_differentiable(r.radii)
+        return _outputs(r)
 
     @staticmethod
     def backward(ctx, g_color, _g_radii, g_depth, g_alpha, g_color2=None):
+        t0 = time.perf_counter()
         lib = _C.load_library()
         m3, col, sc, rot, radii, cbg, color, c2 = ctx.saved_tensors
         V, P = int(m3.shape[0]), int(m3.shape[1])
@@ -444,46 +435,30 @@ class _RasterizeTimedViews(torch.autograd.Function):
                 if t is not None:
                     t.zero_()
         else:
-            gc = g_color.float().contiguous()
-            gd = g_depth.float().contiguous() if g_depth is not None else None
-            ga = g_alpha.float().contiguous() if g_alpha is not None else None
-            g2 = g_color2.float().contiguous() if second else None
+            rows = dict(dL_dcolor=_upstream(g_color), dL_ddepth=_upstream(g_depth), dL_dalpha=_upstream(g_alpha),
+                        color=color, bg_images=cbg, dL_dbg=d_bg, dL_dmeans2D=d_m2,
+                        dL_dcolor2=_upstream(g_color2) if second else None)
             stream = _C._stream(dev)
             g = _C.SetGrads(dL_dcolors=_addr(d_col), dL_dopacity=_addr(d_op), dL_dscales=None if sc_v else _addr(d_sc),
                             dL_drotations=None if rot_v else _addr(d_rot))
+            if second and not c2_v:
+                g.colors2, g.dL_dcolors2 = _addr(c2), _addr(d_c2)
             for si, vs in enumerate(ctx.sets):
-                kmax = _arr(ctypes.c_int, [max(vs.K)])
-                need = int(lib.gsr_set_backward_bytes(vs.V, P, vs.state.num_rendered, int(second)))
-                largest = int(lib.gsr_set_backward_bytes(1, P, kmax, int(second)))
-                work = torch.empty(max(largest, min(need, WORK_BUDGET)), dtype=torch.uint8, device=dev)
+                work = _set_work(lib, vs, second)
+                _set_grads(g, vs, rows, work, accumulate=si > 0)
                 sl = slice(vs.lo, vs.hi)
-                g.dL_dcolor, g.dL_dmeans2D = _addr(gc[sl]), _addr(d_m2[sl])
-                g.dL_ddepth = _addr(gd[sl]) if gd is not None else None
-                g.dL_dalpha = _addr(ga[sl]) if ga is not None else None
-                g.color = _addr(color[sl]) if color is not None else None
-                g.bg_images = _addr(cbg[sl]) if cbg is not None else None
-                g.dL_dbg = _addr(d_bg[sl]) if d_bg is not None else None
                 timed = vs.timed
-                if second:
-                    g.dL_dcolor2 = _addr(g2[sl])
-                    if not c2_v:
-                        g.colors2, g.dL_dcolors2 = _addr(c2), _addr(d_c2)
-                elif c2_v:
+                if c2_v and not second:
                     # the second colour's image took no gradient: the one-colour backward of the first call
                     timed = _C.SetTimed.from_buffer_copy(vs.timed)
                     timed.colors2_v = None
                 tg = _C.SetTimedGrads(dL_dmeans3D_v=_addr(d_m3[sl]), dL_dscales_v=_addr(d_sc[sl]) if sc_v else None,
                                       dL_drotations_v=_addr(d_rot[sl]) if rot_v else None,
                                       dL_dcolors2_v=_addr(d_c2[sl]) if second and c2_v else None)
-                g.accumulate = 1 if si > 0 else 0
-                g.work, g.work_bytes = _addr(work), work.numel()
                 _C._check(lib.gsr_set_timed_backward(vs.scene, vs.state, g, timed, tg, stream))
-        if d_bg is not None:
-            d_bg = d_bg.reshape(ctx.bg_shape)
-        grads = [None, None, d_m3, d_col, d_op, d_sc, d_rot, d_bg, d_c2] + [d_m2[v] for v in range(V)]
-        for k, need in enumerate(ctx.needs_input_grad):
-            if not need:
-                grads[k] = None
+        grads = _masked_grads(ctx, [None, None, d_m3, d_col, d_op, d_sc, d_rot, d_bg, d_c2]
+                              + [d_m2[v] for v in range(V)], bg_at=7)
+        _C.host_mark("bwd_host", t0)
         return tuple(grads)
 
 
@@ -535,15 +510,7 @@ def rasterize_timed_views(settings_list, means3D, means2D_list, opacities, color
     for m2 in means2D_list:
         if tuple(m2.shape) != (P, 3):
             raise ValueError(f"a means2D placeholder has shape {tuple(m2.shape)}, expected ({P}, 3)")
-    s0 = settings_list[0]
-    H, W = int(s0.image_height), int(s0.image_width)
-    if any(int(s.image_height) != H or int(s.image_width) != W for s in settings_list):
-        raise ValueError("all views of a batch must have the same image size")
-    if any(int(s.sh_degree) != int(s0.sh_degree) or float(s.scale_modifier) != float(s0.scale_modifier)
-           or bool(s.prefiltered) != bool(s0.prefiltered) for s in settings_list):
-        raise ValueError("sh_degree, scale_modifier and prefiltered must be shared by the views of a batch")
-    if background is not None and background.numel() != V * H * W * 3:
-        raise ValueError("background must hold (V, H, W, 3) values")
+    _check_views(settings_list, background, size_error=ValueError)
     named = [("means3D", means3D), ("opacities", opacities), ("colors_precomp", colors_precomp), ("scales", scales),
              ("rotations", rotations), ("colors2", colors2)]
     for name, t in named:
