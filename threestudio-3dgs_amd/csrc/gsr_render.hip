@@ -190,6 +190,38 @@ __device__ __forceinline__ float bg_dot3(const float* bg, float d0, float d1, fl
   return fmaf(bg[2], d2, fmaf(bg[1], d1, bg[0] * d0));
 }
 
+// ---------------------------------------------------------------------------------------
+// Blocks the four blend kernels (k_render_fwd, k_render_fwd_tile, bwd_tile of k_render_bwd, k_render_bwd_tw) each
+// write out, kept in step by hand.  Folding them into shared inline functions was tried block by block and every one,
+// down to the 64-lane maximum, changed the instruction schedule and register allocation of the kernels that took it,
+// inside their batch loops included; the kernels' speed rests on those schedules, so the copies stay.  A fix to one
+// copy goes to all of them:
+//   [view]     the per-view pointer offsets at the head of each kernel (vg = rs.v0 + v, tiles, HW);
+//   [pixel]    lane -> pixel of a quadrant: px, py, inside, pid (k_render_fwd_tile has it twice);
+//   [gather]   a, b, c of rec[g], then the second colour embedded (b.w, c.w, d.z) or gathered from col2: twice in
+//              k_render_fwd (with the GSR_EXP_FWD_NOC / GSR_EXP_NOCOL2 timing switches), twice in k_render_fwd_tile,
+//              and the `load` lambda of k_render_bwd_tw (which reads the embedded colours at its staging);
+//   [epilogue] the forwards' per-pixel stores: final_T, n_contrib, colour / depth / alpha, out_col2, the fused
+//              composite or clamp, each under fp contract(off), and the 64-lane quad_maxc maximum;
+//   [prologue] the backwards' per-pixel upstream gradients through the fused composite backward (rs.cbg) or the clamp
+//              alone (rs.ccolor): bwd_tile stores dL/dbg for chunk 0 only, k_render_bwd_tw always;
+//   [cull]     the decode of the forward's cull record, below.
+//
+// The forward's cull record, RenderSet::qbytes: which (listed instance, quadrant) pairs blended at least one pixel.
+// A pair the forward blended nowhere has no backward hit (the same alpha, power and list-position tests), so the
+// backwards read the cull instead of recomputing it.  ImageState::split_mode[1] names the layout (set by a byte
+// memset: its low byte):
+//   1, written by k_render_fwd_tile: byte i = the 4-bit mask of the quadrants instance i blended in;
+//   2, written by k_render_fwd:      byte 4 i + q = 1 when quadrant q blended instance i;
+//   0: none recorded (no forward of this library leaves that for a non-empty list).  k_render_bwd_tw then reads the
+//      conservative quadrant masks the keys carry (rs.qkeys, TilePack::qmask, from bit GSR_QMASK_SHIFT) or, without
+//      those, recomputes the cull; bwd_tile replays every candidate below its quadrant's deepest blend (the replay's
+//      own alpha tests keep that exact).
+// Batches past the last blend are never written and never read.  Readers: bwd_tile takes its own quadrant's bit
+// (qbm / qstride / qsh), k_render_bwd_tw all four as a 4-bit mask (cull_raw / cull_decode); both load a word raw, one
+// batch ahead, and decode it where it is used.
+// ---------------------------------------------------------------------------------------
+
 // Forward: one wave (64 threads) per 8x8 quadrant of a 16x16 tile.  The wave streams the tile's
 // depth-sorted instance list 64 at a time, keeps (ballot compaction, order preserved) only the
 // Gaussians whose alpha >= 1/255 ellipse can reach its quadrant, and blends them with a
@@ -398,10 +430,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_FWD_WPE,
       while (dmk != ~0ull && step(pa, pb, pc, pd, ya, yb, yc, yd) && step(ya, yb, yc, yd, pa, pb, pc, pd)) {
       }
     }
-    // the backward's exact cull (RenderSet::qbytes, layout 2: byte 4 i + q of the set's listed instance i): whether
-    // candidate i blended any pixel of this quadrant (a pair the forward blended nowhere has no backward hit: same
-    // alpha, power and position tests).  Batches past the quadrant's termination are never walked, and the backward
-    // reads only below its deepest blend.
+    // the backward's exact cull ([cull] above, layout 2): whether candidate i blended any pixel of this quadrant
     if (rs.qbytes != nullptr && i < n) {
       qbp = rs.qbytes + 4 * ((size_t)rs.inst_start[v] + range.x + i) + q;
       qbv = keep && ((hbm >> mask_rank(bal)) & 1ull) ? 1u : 0u;
@@ -412,6 +441,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_FWD_WPE,
   }
   if (qbp != nullptr) *qbp = qbv;
   if (inside) {
+    // ([epilogue]: k_render_fwd_tile has the other copy, once per quadrant)
     const size_t pid = (size_t)py * W + px;
     const size_t HW = (size_t)H * W;
     final_T[pid] = T;
@@ -457,6 +487,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_FWD_WPE,
     reinterpret_cast<float4*>(ckpt + (size_t)chunk * GSR_CKPT_FIELDS * 256 + 256)[cpix] =
         make_float4(PrPg.x, PrPg.y, PbPd.x, PbPd.y);
   }
+  // (the 64-lane maximum: the same ladder as k_render_fwd_tile's, per quadrant there)
   uint32_t mc = last_contributor;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) mc = max(mc, (uint32_t)__shfl_xor((int)mc, o, 64));
@@ -747,8 +778,7 @@ __global__ __launch_bounds__(64) void k_render_fwd_tile(RenderSet rs, const uint
       while (dm[q] != ~0ull && step(pa, pb, pc, pd, ya, yb, yc, yd) && step(ya, yb, yc, yd, pa, pb, pc, pd)) {
       }
     }
-    // the backward's cull of this batch: candidate i's 4-bit mask of quadrants it blended in (batches past the last
-    // blend are never read by it)
+    // the backward's cull of this batch ([cull] above, layout 1): candidate i's 4-bit mask of quadrants it blended in
     qbi = qbytes != nullptr && i < n ? i : -1;
     qbv = (uint8_t)(((hb[0] >> lane) & 1ull) | (((hb[1] >> lane) & 1ull) << 1) | (((hb[2] >> lane) & 1ull) << 2) |
                     (((hb[3] >> lane) & 1ull) << 3));
@@ -760,6 +790,7 @@ __global__ __launch_bounds__(64) void k_render_fwd_tile(RenderSet rs, const uint
   for (int q = 0; q < 4; ++q) {
     const int px = tx0 + (q & 1) * 8 + (lane & 7), py = ty0 + (q >> 1) * 8 + (lane >> 3);
     if (inside[q]) {
+      // ([epilogue]: k_render_fwd has the other copy, with the comments)
       const size_t pid = (size_t)py * W + px;
       const float Tq = T[q];
       final_T[pid] = Tq;
@@ -795,6 +826,7 @@ __global__ __launch_bounds__(64) void k_render_fwd_tile(RenderSet rs, const uint
         cp[2 * HWs] = fminf(fmaxf(p2, 0.0f), 1.0f);
       }
     }
+    // (the 64-lane maximum: the same ladder as k_render_fwd's)
     uint32_t mc = last[q];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mc = max(mc, (uint32_t)__shfl_xor((int)mc, o, 64));
@@ -929,28 +961,28 @@ void launch_render_forward(const RenderSet& rs, const GeomState& g, const uint32
                            long long instances, hipStream_t stream) {
   const int nt = rs.gx * rs.gy;
   if (nt <= 0 || rs.V <= 0) return;
-  if (fwd_tile_kernel(instances, (long long)rs.V * rs.P, rs.V)) {
-    const dim3 grid(block_grid(rs, 4));
-    g_blend_kernel[0] = rs.col2 != nullptr ? "k_render_fwd_tile<true>" : "k_render_fwd_tile<false>";
-    if (rs.col2 != nullptr)
-      hipLaunchKernelGGL(k_render_fwd_tile<true>, grid, dim3(64), 0, stream, rs, (const uint2*)img.ranges,
-                         sorted_gauss, (const GaussRec*)g.rec, out_color, out_depth, out_alpha, img.final_T,
-                         img.n_contrib, img.quad_maxc);
-    else
-      hipLaunchKernelGGL(k_render_fwd_tile<false>, grid, dim3(64), 0, stream, rs, (const uint2*)img.ranges,
-                         sorted_gauss, (const GaussRec*)g.rec, out_color, out_depth, out_alpha, img.final_T,
-                         img.n_contrib, img.quad_maxc);
-  } else {
-    auto kern = rs.col2 != nullptr ? (rs.ckpt != nullptr ? k_render_fwd<true, true> : k_render_fwd<true, false>)
-                                   : (rs.ckpt != nullptr ? k_render_fwd<false, true> : k_render_fwd<false, false>);
-    g_blend_kernel[0] = rs.col2 != nullptr ? (rs.ckpt != nullptr ? "k_render_fwd<true, true>" : "k_render_fwd<true, false>")
-                                           : (rs.ckpt != nullptr ? "k_render_fwd<false, true>" : "k_render_fwd<false, false>");
-    hipLaunchKernelGGL(kern, dim3(block_grid(rs, 16)), dim3(64), 0, stream, rs, (const uint2*)img.ranges,
-                       sorted_gauss, (const GaussRec*)g.rec, out_color, out_depth, out_alpha, img.final_T,
-                       img.n_contrib, img.quad_maxc);
-    if (rs.ckpt != nullptr)
-      hipLaunchKernelGGL(k_ckpt_suffix, dim3(rs.V * nt), dim3(256), 0, stream, rs, (const uint32_t*)img.quad_maxc);
-  }
+  // the kernel and the name the profiler gives it, chosen together (both forwards take the same arguments)
+  struct Fwd {
+    void (*kernel)(RenderSet, const uint2*, const uint32_t*, const GaussRec*, float*, float*, float*, float*, uint32_t*,
+                   uint32_t*);
+    const char* name;
+  };
+  static const Fwd tile_wave[2] = {{k_render_fwd_tile<true>, "k_render_fwd_tile<true>"},
+                                   {k_render_fwd_tile<false>, "k_render_fwd_tile<false>"}};  // [one colour]
+  static const Fwd quadrant_wave[2][2] = {{{k_render_fwd<true, true>, "k_render_fwd<true, true>"},
+                                           {k_render_fwd<true, false>, "k_render_fwd<true, false>"}},
+                                          {{k_render_fwd<false, true>, "k_render_fwd<false, true>"},
+                                           {k_render_fwd<false, false>, "k_render_fwd<false, false>"}}};
+  // (quadrant_wave[one colour][no checkpoints])
+  const bool tile = fwd_tile_kernel(instances, (long long)rs.V * rs.P, rs.V);
+  const bool one = rs.col2 == nullptr, ck = rs.ckpt != nullptr;
+  const Fwd& f = tile ? tile_wave[one] : quadrant_wave[one][!ck];
+  g_blend_kernel[0] = f.name;
+  hipLaunchKernelGGL(f.kernel, dim3(block_grid(rs, tile ? 4 : 16)), dim3(64), 0, stream, rs, (const uint2*)img.ranges,
+                     sorted_gauss, (const GaussRec*)g.rec, out_color, out_depth, out_alpha, img.final_T, img.n_contrib,
+                     img.quad_maxc);
+  if (!tile && ck)
+    hipLaunchKernelGGL(k_ckpt_suffix, dim3(rs.V * nt), dim3(256), 0, stream, rs, (const uint32_t*)img.quad_maxc);
   hipLaunchKernelGGL(k_tile_info, dim3(rs.V * div_up(nt, 256)), dim3(256), 0, stream, rs,
                      (const uint2*)img.ranges, (const uint32_t*)img.quad_maxc, sorted_gauss,
                      (const GaussRec*)g.rec, img.tile_info, img.cut);
@@ -1030,6 +1062,7 @@ __device__ __forceinline__ void bwd_tile(BwdLDS& s, const RenderSet& rs, int v, 
     if (dL_dalpha) dpix_a = dL_dalpha[pid];
     if (rs.cbg != nullptr) {
       // fused composite backward: dL/dcomp masked by the clamp -> dL/dcolor, dL/dalpha, dL/dbg
+      // ([prologue]: k_render_bwd_tw has the other copy, which stores dL/dbg unconditionally)
 #pragma clang fp contract(off)
       const float am = 1.0f - (1.0f - T_final);
       const float* bgi = rs.cbg + ((size_t)v * HW + pid) * 3;
@@ -1113,9 +1146,7 @@ __device__ __forceinline__ void bwd_tile(BwdLDS& s, const RenderSet& rs, int v, 
   // the forward's per-instance quadrant cull (ImageState::split_mode[1]): the cull is read, one
   // batch ahead, instead of recomputed (both bounds are conservative: a pair either keeps has no blend beyond
   // the other's, so the sums agree)
-  // (layout 1, the tile-wave forward: byte i = the 4-bit mask of instance i; layout 2, the quadrant-wave forward:
-  // byte 4 i + q = quadrant q keeps instance i)
-  // (split_mode[1] is set by a byte memset: its low byte is the layout)
+  // ([cull] above has the layouts; k_render_bwd_tw's cull_raw / cull_decode are the four-quadrant reader)
   const uint32_t qlayout = rs.qbytes != nullptr && rs.split_mode != nullptr ? (rs.split_mode[1] & 0xffu) : 0u;
   const size_t qpos0 = (size_t)rs.inst_start[v] + range.x;
   const uint8_t* const qbm = qlayout == 0u ? nullptr : qlayout == 1u ? rs.qbytes + qpos0 : rs.qbytes + 4 * qpos0 + q;
@@ -1376,9 +1407,7 @@ __device__ __forceinline__ void bwd_tile(BwdLDS& s, const RenderSet& rs, int v, 
 #ifdef GSR_EXP_NOCULL
     if (rel_l >= lo && rel_l < qmaxc) keep = s.s0[lane].x > -1e30f;
 #else
-    // (every forward records its masks — layout 1 or 2 — whenever a list is non-empty; without them, which no
-    // forward of this library leaves, every candidate before the quadrant's deepest blend is replayed: the replay's
-    // own alpha tests keep that exact)
+    // (without a recorded cull every candidate before the quadrant's deepest blend is replayed: [cull] above)
     keep = rel_l >= lo && rel_l < qmaxc && (qbm == nullptr || ((qcur >> qsh) & 1u));
 #endif
     // the next batch's cull, read after this one's into the same register (a copy at the loop latch waited for
@@ -1611,16 +1640,19 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(
     const float* __restrict__ final_Ts, const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dcolor,
     const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha, float4* __restrict__ grow,
     unsigned long long* __restrict__ reach) {
-  constexpr int NG = TWO ? NGV2 : NGV;  // raw sums per (candidate, quadrant)
-  constexpr int NM = TWO ? 15 : NGV;    // moments per candidate
-  constexpr int RW = TWO ? 4 : 3;       // float4 per gradient row
+  // (only the two-colour kernel is launched; the template header stays for its profiler name k_render_bwd_tw<true>,
+  // which bench.py, tests/test_gpu_blend_lengths.py and the counters under profiles/ read)
+  static_assert(TWO, "k_render_bwd_tw: the one-colour backward is k_render_bwd");
+  constexpr int NG = NGV2;  // raw sums per (candidate, quadrant)
+  constexpr int NM = 15;    // moments per candidate
+  constexpr int RW = 4;     // float4 per gradient row
   constexpr int NQ = 4;                 // quadrants per wave
   __shared__ float4 s0[65], s1[65], s2[65];
   __shared__ float4 s3[65];  // (b, b2) of the interleaved colours
   __shared__ uint32_t slot[64];
   __shared__ uint32_t list[64];                  // the current quadrant: first hit | hits << 16
   __shared__ float4 hits[GSR_HCAP_TW];            // (u, u_1, w, pixel) of the current quadrant's blends
-  __shared__ float4 planes[TWO ? 128 : 64];       // the current quadrant's dL/dpixel per pixel
+  __shared__ float4 planes[128];                  // the current quadrant's dL/dpixel per pixel, both colours
   int v, tile, q_unused;
   if (!block_map<4>(blockIdx.x, rs, v, tile, q_unused)) return;
   GSR_TL_BEGIN
@@ -1677,6 +1709,7 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(
       if (dL_ddepth) dd = dL_ddepth[pid];
       if (dL_dalpha) da = dL_dalpha[pid];
       if (rs.cbg != nullptr) {
+        // ([prologue]: bwd_tile has the other copy, which stores dL/dbg for its chunk 0 only)
 #pragma clang fp contract(off)
         const float am = 1.0f - (1.0f - T_final);
         const float* bgi = rs.cbg + ((size_t)v * HW + pid) * 3;
@@ -1703,7 +1736,7 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(
       }
     }
     float e[3] = {0.f, 0.f, 0.f};
-    if (TWO && inside) {
+    if (inside) {
       const float* d2 = rs.dpix2 + (size_t)v * 3 * HW;
       e[0] = d2[pid];
       e[1] = d2[HW + pid];
@@ -1714,7 +1747,7 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(
     de2[j] = f2{d[2], e[2]};
     dpd[j] = dd;
     dpa0[j] = f2{da, -0.0f};
-    nbgs[j] = f2{-T_final * bg_dot3(bg, d[0], d[1], d[2]), TWO ? -T_final * bg_dot3(bg, e[0], e[1], e[2]) : 0.f};
+    nbgs[j] = f2{-T_final * bg_dot3(bg, d[0], d[1], d[2]), -T_final * bg_dot3(bg, e[0], e[1], e[2])};
     SS2[j] = f2{0.f, 0.f};
     Sd[j] = 0.f;
   }
@@ -1740,19 +1773,12 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(
     }
     {
       nc = r[2];
-      if (rs.col2 != nullptr && !(TWO && emb)) {  // (embedded: the record's b.w, c.w, d.z, read at the staging)
-        const float4 c2 = make_float4(rs.col2[3 * g], rs.col2[3 * g + 1], rs.col2[3 * g + 2], 0.f);
-        if (TWO)
-          n2 = c2;
-        else  // the second rasterizer call's colours replace the first's
-          nc = c2;
-      }
+      if (rs.col2 != nullptr && !emb)  // (embedded: the record's b.w, c.w, d.z, read at the staging)
+        n2 = make_float4(rs.col2[3 * g], rs.col2[3 * g + 1], rs.col2[3 * g + 2], 0.f);
     }
   };
-  // The cull is read, not recomputed: the forward's exact masks when it recorded them (ImageState::split_mode[1];
-  // layout 1, the tile-wave forward: byte i = the 4-bit mask of the quadrants instance i blended in; layout 2, the
-  // quadrant-wave forward: byte 4 i + q = quadrant q blended instance i — a pair the forward blended nowhere has no
-  // backward hit), else the quadrant masks the keys carry (TilePack::qmask, conservative).
+  // The cull is read, not recomputed: the forward's exact masks when it recorded them, else the quadrant masks the
+  // keys carry ([cull] above has the layouts; bwd_tile's qbm / qstride / qsh are the one-quadrant reader)
   const uint32_t qlayout = rs.qbytes != nullptr && rs.split_mode != nullptr ? (rs.split_mode[1] & 0xffu) : 0u;
   const uint8_t* const qbm = qlayout != 0u ? rs.qbytes + (qlayout == 2u ? 4 : 1) * ((size_t)rs.inst_start[v] + range.x)
                                            : nullptr;
@@ -1805,31 +1831,27 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(
       C[3] = fmaf(u, dx * dx, C[3]);
       C[4] = fmaf(u, dx * dy, C[4]);
       C[5] = fmaf(u, dy * dy, C[5]);
-      const float4 d = planes[TWO ? 2 * p : p];
+      const float4 d = planes[2 * p];
       C[6] = fmaf(w, d.x, C[6]);
       C[7] = fmaf(w, d.y, C[7]);
       C[8] = fmaf(w, d.z, C[8]);
       C[9] = fmaf(w, d.w, C[9]);
-      if constexpr (TWO) {
-        const float u1 = hv.y;
-        const float4 d2 = planes[2 * p + 1];
-        C[10 % NG] += u1;
-        C[11 % NG] = fmaf(u1, dx, C[11 % NG]);
-        C[12 % NG] = fmaf(u1, dy, C[12 % NG]);
-        C[13 % NG] = fmaf(w, d2.x, C[13 % NG]);
-        C[14 % NG] = fmaf(w, d2.y, C[14 % NG]);
-        C[15 % NG] = fmaf(w, d2.z, C[15 % NG]);
-      }
+      const float u1 = hv.y;
+      const float4 d2 = planes[2 * p + 1];
+      C[10] += u1;
+      C[11] = fmaf(u1, dx, C[11]);
+      C[12] = fmaf(u1, dy, C[12]);
+      C[13] = fmaf(w, d2.x, C[13]);
+      C[14] = fmaf(w, d2.y, C[14]);
+      C[15] = fmaf(w, d2.z, C[15]);
     }
 #pragma unroll
     for (int f = 0; f < 10; ++f) m[f] = C[f];
-    if (TWO) {
-      m[10 % NM] = C[11 % NG];
-      m[11 % NM] = C[12 % NG];
-      m[12 % NM] = C[13 % NG];
-      m[13 % NM] = C[14 % NG];
-      m[14 % NM] = C[15 % NG];
-    }
+    m[10] = C[11];
+    m[11] = C[12];
+    m[12] = C[13];
+    m[13] = C[14];
+    m[14] = C[15];
   };
   // the pending pairs of this wave's quadrant j (lanes whose bit is set) into the running total
   auto flush = [&](const int j, const unsigned long long pend) {
@@ -1866,12 +1888,10 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(
       rv[0] = make_float4(dmx, dmy, -0.5f * o * m[3], -0.5f * o * m[4]);
     }
     rv[1] = make_float4(-0.5f * o * m[5], m[0], m[6], m[7]);
-    rv[2] = TWO ? make_float4(m[8], m[9], m[12 % NM], m[13 % NM]) : make_float4(m[8], m[9], 0.f, 0.f);
-    if (TWO) {
-      const float dmx1 = mean_grad(k, ddelx_dx, gb.x, ga.z, m[10 % NM], m[11 % NM]);
-      const float dmy1 = mean_grad(k, ddely_dy, ga.w, ga.z, m[11 % NM], m[10 % NM]);
-      rv[RW - 1] = make_float4(m[14 % NM], dmx1, dmy1, 0.f);
-    }
+    rv[2] = make_float4(m[8], m[9], m[12], m[13]);
+    const float dmx1 = mean_grad(k, ddelx_dx, gb.x, ga.z, m[10], m[11]);
+    const float dmy1 = mean_grad(k, ddely_dy, ga.w, ga.z, m[11], m[10]);
+    rv[3] = make_float4(m[14], dmx1, dmy1, 0.f);
   };
   auto store_row = [&]() {
     float4* row = grow + RW * (size_t)rslot;
@@ -1890,9 +1910,8 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(
     const float4 ca = make_float4(vcopy(na.x), vcopy(na.y), vcopy(na.z), vcopy(na.w));
     const float4 cb = make_float4(vcopy(nb.x), vcopy(nb.y), vcopy(nb.z), 0.f);
     const float4 cc = make_float4(vcopy(nc.x), vcopy(nc.y), vcopy(nc.z), 0.f);
-    const float4 c2 = !TWO ? zero4
-                      : emb ? make_float4(vcopy(nb.w), vcopy(nc.w), vcopy(nd.z), 0.f)
-                            : make_float4(vcopy(n2.x), vcopy(n2.y), vcopy(n2.z), 0.f);
+    const float4 c2 = emb ? make_float4(vcopy(nb.w), vcopy(nc.w), vcopy(nd.z), 0.f)
+                          : make_float4(vcopy(n2.x), vcopy(n2.y), vcopy(n2.z), 0.f);
     const uint32_t cdx = __float_as_uint(vcopy(nd.x)), cdy = __float_as_uint(vcopy(nd.y));
     const uint32_t cgo = __float_as_uint(vcopy(__uint_as_float(ngo)));
     const int rel_c = h - 1 - lane;
@@ -1918,7 +1937,7 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(
       }
     }
     if (staged) {
-      // colours interleaved with the second colours (zeros for one colour): (r, r2, g, g2), (b, b2)
+      // colours interleaved with the second colours: (r, r2, g, g2), (b, b2)
       s2[lane] = make_float4(cc.x, c2.x, cc.y, c2.y);
       s3[lane] = make_float4(cc.z, c2.z, 0.f, 0.f);
     }
@@ -1951,8 +1970,8 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(
       const unsigned long long kq = __ballot((keep4 >> q) & 1u);
       if (kq == 0ull) continue;
       // this quadrant's dL/dpixel planes for the sums
-      planes[TWO ? 2 * lane : lane] = make_float4(de0[j].x, de1[j].x, de2[j].x, dpd[j]);
-      if (TWO) planes[2 * lane + 1] = make_float4(de0[j].y, de1[j].y, de2[j].y, 0.f);
+      planes[2 * lane] = make_float4(de0[j].x, de1[j].x, de2[j].x, dpd[j]);
+      planes[2 * lane + 1] = make_float4(de0[j].y, de1[j].y, de2[j].y, 0.f);
       const f2 pxy = {lxf + (float)((q & 1) * 8), lyf + (float)((q >> 1) * 8)};
       int fill = 0;
       unsigned long long pend = 0ull, rest = kq;
@@ -1989,13 +2008,8 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(
         cdp = __builtin_elementwise_fma(f2{gc.x, gc.y}, de0[j], cdp);
         const f2 dif = cdp - SS2[j];                            // (cd - S, cd2 - S2)
         const f2 ibg = f2{inv_1ma, inv_1ma} * nbgs[j];          // (inv nbg, inv nbg2)
-        float u, u1 = 0.f;
-        if (TWO) {
-          u1 = g_eff * fmaf(T[j], fmaf(gb.z - Sd[j], dpd[j], dif.x), ibg.x);
-          u = fmaf(g_eff, fmaf(T[j], dif.y, ibg.y), u1);
-        } else {
-          u = g_eff * fmaf(T[j], fmaf(gb.z - Sd[j], dpd[j], dif.x), ibg.x);
-        }
+        const float u1 = g_eff * fmaf(T[j], fmaf(gb.z - Sd[j], dpd[j], dif.x), ibg.x);
+        const float u = fmaf(g_eff, fmaf(T[j], dif.y, ibg.y), u1);
         const float w = a_eff * T[j];
         SS2[j] = __builtin_elementwise_fma(f2{a_eff, a_eff}, cdp, f2{oma, oma} * SS2[j]);  // (S, S2)
         Sd[j] = fmaf(a_eff, gb.z, oma * Sd[j]);
