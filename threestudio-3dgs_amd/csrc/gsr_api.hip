@@ -81,6 +81,16 @@ static int tile_keys_mode() {
 }
 static TilePack set_tile_pack(int P, int W, int H) { return tile_pack(P, W, H, tile_keys_mode()); }
 
+// GSR_EMIT_SPANS=0: the emission evaluates every Gaussian's rows from its record, as a geometry buffer without span
+// words makes it (the bitwise tests and A/B timing of the span-word gather); read once per process.
+static bool emit_spans_mode() {
+  static const bool on = [] {
+    const char* e = getenv("GSR_EMIT_SPANS");
+    return !(e != nullptr && strcmp(e, "0") == 0);
+  }();
+  return on;
+}
+
 static int effective_degree(int degree, int M) {
   // the reference reads sqrt(M)-1 coefficients at most (pred-normal pass quirk)
   int dm = (int)std::lround(std::sqrt((double)(M > 0 ? M : 1))) - 1;
@@ -442,7 +452,7 @@ int gsr_set_render(const gsr_set_scene* scene, const gsr_set_state* state, const
     PhaseScope ps(GSR_PHASE_BINNING, s);
     GSR_HIP_CHECK(hipMemsetAsync(img.ranges, 0, sizeof(uint2) * (size_t)V * gx * gy, s));
     if (total > 0) {
-      launch_emit(V, P, width, g, inst, c.tp, b.key[0], b.val[0], s);
+      launch_emit(V, P, width, g, inst, c.tp, emit_spans_mode(), b.key[0], b.val[0], s);
       const int res =
           seg_sort(b.key, b.val, false, inst, c.tp.gbits, c.tp.tile_bits, b.sort_counts, b.sort_totals, s);
       if (res != c.tres) return fail(GSR_EHIP, "%s", "internal: tile sort buffer");

@@ -245,11 +245,21 @@ struct EmitLDS {
 // QM (unpacked keys): each key also carries the instance's quadrant mask (GSR_QMASK_SHIFT): per row the
 // quadrant-column ranges of its two 8-pixel bands (span_quads, the span_row bound at half the tile size), per
 // instance four integer compares.
-template <bool QM>
+//
+// SW (keys without quadrant masks): a lane gathers its Gaussian's packed span word (GeomState::spans, 8 B of a line 16
+// Gaussians share) in the record's place and takes the row count and each row's [t0, t1) from it: no record, no
+// span_prep, no span_row.  A lane whose word is "not encodable" loads the record and runs the rows as before, in
+// the same wave (its roff[] entry carries GSR_EMIT_REC; an encodable lane's word sits in its rect[] slot); so does
+// every lane of a geometry buffer that carries no words (drange[132] == 0).  The word holds what span_row returned
+// in the preprocess, so the lists are the same either way.  !SW is the kernel without any of this.
+#define GSR_EMIT_REC 0x80000000u  // roff[] flag: the Gaussian's rows come from its record (roff itself < 2^23)
+template <bool QM, bool SW>
 __global__ __launch_bounds__(64) void k_emit(int P, int nbe, int grid_x, GeomState g, SegInfo inst, int gbits,
                                              uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  static_assert(!(QM && SW), "span words serve the packed keys only (the quadrant masks need the conic)");
   const uint32_t* __restrict__ order = g.sorted_dval();
   const uint32_t* __restrict__ dkeys = g.sorted_dkey();
+  const bool words = SW && g.drange[132] != 0u;
   __shared__ EmitLDS<QM> s;
   const int nw = div_up(nbe, GSR_EMIT_GROUPS);
   const int v = blockIdx.x / nw;
@@ -268,7 +278,9 @@ __global__ __launch_bounds__(64) void k_emit(int P, int nbe, int grid_x, GeomSta
     n_gi = r < P ? (order[vo + r] & g.vmask()) : 0u;
     n_vis = r < P && dkeys[vo + r] != 0xFFFFFFFFu;
     n_koff = g.kept_counts[(size_t)v * nbe + lb];
-    if (n_vis) {
+    if (SW) {
+      n_d = n_vis && words ? g.spans[vo + n_gi] : make_uint2(0u, 0u);  // (the word travels where the rect does)
+    } else if (n_vis) {
       const GaussRec& rc = g.rec[vo + n_gi];
       const uint4 d = rc.d;
       n_d = make_uint2(d.x, d.y);
@@ -281,23 +293,39 @@ __global__ __launch_bounds__(64) void k_emit(int P, int nbe, int grid_x, GeomSta
     const uint32_t gi = n_gi;
     const bool vis = n_vis;
     const float4 ra = n_ra, rb = n_rb;
-    const uint2 d = n_d;
+    uint2 d = n_d;
     uint32_t kbase = n_koff;
-    if (lb + 1 < lb1) fetch(lb + 1);
-    uint32_t cnt = 0u, h = 0u;
-    if (vis) {
-      const uint32_t wd = (d.y & 0xffffu) - (d.x & 0xffffu);
-      h = (d.y >> 16) - (d.x >> 16);
-      cnt = wd * h;  // rectangle tiles
-      if (cnt == 0u) h = 0u;
+    auto rect_rows = [](uint2 rect) {  // rectangle rows (0: no rectangle tiles)
+      const uint32_t wd = (rect.y & 0xffffu) - (rect.x & 0xffffu), hh = (rect.y >> 16) - (rect.x >> 16);
+      return wd * hh == 0u ? 0u : hh;
+    };
+    bool fb = !SW && vis;  // this lane's rows come from its record
+    uint32_t h = 0u;
+    if (SW && vis) {
+      const uint64_t w = (uint64_t)d.x | (uint64_t)d.y << 32;
+      if (span_word_ok(w)) {
+        h = (uint32_t)span_word_rows(w);
+      } else {
+        // not encodable (rare, divergent): the record after all, loaded and used up here, so that no load of this
+        // branch is pending where the paths meet (the next group's gather below then stays in flight over the rows)
+        fb = true;
+        const GaussRec& rc = g.rec[vo + gi];
+        const uint4 rd = rc.d;
+        const float4 fa = rc.a, fb4 = rc.b;
+        d = make_uint2(rd.x, rd.y);
+        h = rect_rows(d);
+        if (h) s.sp[lane] = span_prep(fa.x, fa.y, fa.z, fa.w, fb4.x, fb4.y);
+      }
     }
+    if (lb + 1 < lb1) fetch(lb + 1);
+    if (!SW && vis) h = rect_rows(d);
     const uint32_t rincl = wave_incl_sum_dpp(h);
     const uint32_t roff = rincl - h;
     const uint32_t R = (uint32_t)__builtin_amdgcn_readlane((int)rincl, 63);
     s.gi[lane] = gi;
-    s.roff[lane] = roff;
+    s.roff[lane] = SW && fb ? roff | GSR_EMIT_REC : roff;
     s.rect[lane] = d;
-    if (h) s.sp[lane] = span_prep(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y);
+    if (!SW && h) s.sp[lane] = span_prep(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y);
     uint32_t carry = 0u;  // 1 + owner of the previous chunk's last row
     for (uint32_t r0 = 0; r0 < R; r0 += 64) {
       s.own[lane] = 0u;
@@ -311,10 +339,18 @@ __global__ __launch_bounds__(64) void k_emit(int P, int nbe, int grid_x, GeomSta
       if (r < R) {
         const uint32_t ow = ow1 - 1u;
         const uint2 rc = s.rect[ow];
-        const int xmin = (int)(rc.x & 0xffffu), xmax = (int)(rc.y & 0xffffu);
-        const int row = (int)(rc.x >> 16) + (int)(r - s.roff[ow]);
-        int t0, t1;
-        span_row(s.sp[ow], row, xmin, xmax, t0, t1);
+        const uint32_t ro = s.roff[ow];
+        int row, t0, t1;
+        if (!SW || (ro & GSR_EMIT_REC)) {
+          const int xmin = (int)(rc.x & 0xffffu), xmax = (int)(rc.y & 0xffffu);
+          row = (int)(rc.x >> 16) + (int)(r - (SW ? ro & ~GSR_EMIT_REC : ro));
+          span_row(s.sp[ow], row, xmin, xmax, t0, t1);
+        } else {
+          const uint64_t w = (uint64_t)rc.x | (uint64_t)rc.y << 32;
+          const int i = (int)(r - ro);
+          row = span_word_row0(w) + i;
+          span_word_row(w, i, t0, t1);
+        }
         kc = (uint32_t)(t1 - t0);
         tile0 = (uint32_t)row * (uint32_t)grid_x + (uint32_t)t0;
         rg = s.gi[ow];
@@ -397,17 +433,13 @@ void launch_binning_counts(int V, int P, const GeomState& g, hipStream_t stream)
   hipLaunchKernelGGL(k_inst_scan, dim3(V), dim3(1024), 0, stream, P > 0 ? nbe : 0, g);
 }
 
-void launch_emit(int V, int P, int W, const GeomState& g, const SegInfo& inst, const TilePack& tp, uint32_t* keys,
-                 uint32_t* vals, hipStream_t stream) {
+void launch_emit(int V, int P, int W, const GeomState& g, const SegInfo& inst, const TilePack& tp, bool use_spans,
+                 uint32_t* keys, uint32_t* vals, hipStream_t stream) {
   if (V <= 0 || P <= 0) return;
   const int nbe = GeomState::dup_blocks(P);
   const dim3 grid(V * div_up(nbe, GSR_EMIT_GROUPS));
-  if (tp.qmask)
-    hipLaunchKernelGGL(k_emit<true>, grid, dim3(64), 0, stream, P, nbe, div_up(W, GSR_TILE_X), g, inst, tp.gbits,
-                       keys, vals);
-  else
-    hipLaunchKernelGGL(k_emit<false>, grid, dim3(64), 0, stream, P, nbe, div_up(W, GSR_TILE_X), g, inst, tp.gbits,
-                       keys, vals);
+  auto* kernel = tp.qmask ? k_emit<true, false> : use_spans ? k_emit<false, true> : k_emit<false, false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(64), 0, stream, P, nbe, div_up(W, GSR_TILE_X), g, inst, tp.gbits, keys, vals);
 }
 
 void launch_tile_ranges(SegInfo inst, int n_tiles, const TilePack& tp, const uint32_t* keys, uint2* ranges,

@@ -19,6 +19,8 @@
 #include <string.h>
 #include <stdint.h>
 
+#include "gsr_span_word.h"
+
 #define GSR_TILE_X 16
 #define GSR_TILE_Y 16
 #define GSR_TILE_PIX (GSR_TILE_X * GSR_TILE_Y)  // 256 pixels = 4 waves of 64
@@ -216,12 +218,15 @@ struct GeomState {
   __host__ __device__ uint32_t vsent() const { return vbits > 26 ? 0u : (1u << (32 - vbits)) - 1u; }
   uint32_t* drange;          // depth key range of the set: [0, 64) min slots, [64, 128) max slots,
                              // [128] = min visible key, [129] = 1 if 3 depth-sort passes suffice,
-                             // [130..131] = the colors2 pointer embedded in the records (0 = none)
+                             // [130..131] = the colors2 pointer embedded in the records (0 = none),
+                             // [132] = 1 when the set's preprocess wrote spans[] (0: the buffer carries none)
   // the depth-sorted (keys, Gaussians) of every view: the 4th pass's output, or the 3rd's when it was skipped
   __device__ const uint32_t* sorted_dval() const { return drange[129] ? dval[1] : dval[0]; }
   __device__ const uint32_t* sorted_dkey() const { return drange[129] ? dkey[1] : dkey[0]; }
   uint32_t* counters;        // [0, V) rectangle tiles K of each view (the reference's num_rendered),
                              // [V, 2V) visible Gaussians, [2V, 3V) kept list instances
+  uint2* spans;              // [V][P] the packed span word of each visible Gaussian (gsr_span_word.h; x = low half):
+                             // what the emission gathers in the record's place; undefined for culled Gaussians
   static int sort_blocks(int P) { return div_up(P > 0 ? P : 1, GSR_SORT_TILE); }
   static int dup_blocks(int P) { return div_up(P > 0 ? P : 1, GSR_DUP_TILE); }
   static int goff_blocks(int P) { return div_up(P > 0 ? P : 1, GSR_GOFF_TILE); }
@@ -245,7 +250,8 @@ struct GeomState {
     g.vis_part = c.take<uint32_t>(nv * goff_blocks(P));
     g.vbits = 1;
     while (g.vbits < 32 && (1ull << g.vbits) < (unsigned long long)(P > 1 ? P : 2)) ++g.vbits;
-    g.drange = c.take<uint32_t>(132);
+    g.drange = c.take<uint32_t>(133);
+    g.spans = c.take<uint2>(n);  // (carved last: the arrays before it stay where they were)
     if (bytes) *bytes = align_up(c.off, 256);
     return g;
   }

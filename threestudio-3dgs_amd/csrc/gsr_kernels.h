@@ -65,8 +65,9 @@ void launch_preprocess(const PreprocessArgs& a, const SetCams& cams, const GeomS
 void launch_binning_counts(int V, int P, const GeomState& g, hipStream_t stream);
 // vals == nullptr: packed keys (tile << gbits | Gaussian)
 // dkeys = the depth sort's key buffer (sorted depth keys; culled = ~0)
-void launch_emit(int V, int P, int W, const GeomState& g, const SegInfo& inst, const TilePack& tp, uint32_t* keys,
-                 uint32_t* vals, hipStream_t stream);
+// use_spans: packed keys gather the preprocess's span words where the geometry buffer carries them (k_emit)
+void launch_emit(int V, int P, int W, const GeomState& g, const SegInfo& inst, const TilePack& tp, bool use_spans,
+                 uint32_t* keys, uint32_t* vals, hipStream_t stream);
 // per-tile [start, end) of each view's sorted list, by search (k_tile_bounds)
 void launch_tile_ranges(SegInfo inst, int n_tiles, const TilePack& tp, const uint32_t* keys, uint2* ranges,
                         hipStream_t stream);

@@ -7,7 +7,8 @@
 // Gaussians' parameters are read once per block (SH staged through LDS with coalesced 16-byte loads
 // instead of 3M strided dword loads per thread), the 3D covariance is built once, and the views
 // are walked in turn.  Writes per (view, Gaussian) the 64-byte render record (incl. tile rect and
-// clamp flags), radius, rectangle / kept tile counts and the depth-sort key (culled: ~0, which
+// clamp flags), radius, rectangle / kept tile counts, the packed span word of the rows the kept count walks
+// (gsr_span_word.h: what the emission gathers) and the depth-sort key (culled: ~0, which
 // sorts after every visible depth).
 #include "gsr_kernels.h"
 #include "gsr_math.h"
@@ -131,6 +132,7 @@ __device__ __forceinline__ void preprocess_body(const PreprocessArgs& a, const S
     }
     int radius = 0;
     uint2 tiles = make_uint2(0u, 0u);
+    uint64_t word = GSR_SPAN_NONE;  // the rows' kept spans packed for the emission (gsr_span_word.h)
     uint32_t dkey = 0xFFFFFFFFu;  // culled: sorts after every visible depth
     // near-plane cull on the view-space depth (in_frustum of the reference)
     const float3 p_view = xform_point4x3(p_orig, viewmatrix);
@@ -172,10 +174,12 @@ __device__ __forceinline__ void preprocess_body(const PreprocessArgs& a, const S
           radius = r;
           uint32_t kept = 0;
           const SpanPrep sp = span_prep(rec.a.x, rec.a.y, rec.a.z, rec.a.w, rec.b.x, rec.b.y);
+          word = span_word_head(ymin, ymax - ymin);
           for (int ty = ymin; ty < ymax; ++ty) {
             int t0, t1;
             span_row(sp, ty, xmin, xmax, t0, t1);
             kept += (uint32_t)(t1 - t0);
+            word = span_word_put(word, ty - ymin, t0, t1);
           }
           tiles = make_uint2((uint32_t)area, kept);
           dkey = __float_as_uint(p_view.z);  // > 0.2: float bits are monotone in depth
@@ -185,6 +189,7 @@ __device__ __forceinline__ void preprocess_body(const PreprocessArgs& a, const S
     if (valid) {
       a.radii[vi] = radius;
       g.tiles[vi] = tiles;
+      g.spans[vi] = make_uint2((uint32_t)word, (uint32_t)(word >> 32));
       g.dkey[0][vi] = dkey;
       // the depth sort's value: index | kept tiles (k_inst_count reads them in depth order, streaming)
       const uint32_t ks = g.vsent();
@@ -231,6 +236,7 @@ __global__ void k_depth_range_init(uint32_t* drange, unsigned long long col2) {
   drange[threadIdx.x] = 0xFFFFFFFFu;
   drange[64 + threadIdx.x] = 0u;
   if (threadIdx.x < 2) drange[130 + threadIdx.x] = (uint32_t)(col2 >> (32 * threadIdx.x));  // (see GaussRec)
+  if (threadIdx.x == 2) drange[132] = 1u;  // every preprocess kernel writes the span words (GeomState::spans)
 }
 
 // Fold the 64 slots: [128] = smallest visible key, [129] = 1 when every rebased visible key is below
