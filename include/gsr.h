@@ -179,7 +179,9 @@ int gsr_backward(int P, int degree, int M, int K, int width, int height, const f
 #define GSR_GRAD_CHUNK_ALIGN 4096
 
 /* What gsr_set_preprocess, gsr_set_render and gsr_set_backward all take: the Gaussians (shapes and the
- * exactly-one-of rules as for gsr_forward_preprocess; M is ignored without shs) and the V cameras. */
+ * exactly-one-of rules as for gsr_forward_preprocess; M is ignored without shs) and the V cameras.  With shs, 1 <= M <= 50: the
+ * per-Gaussian backward stages 256 rows of 3M floats in the CU's 160 KB of LDS; a wider row is rejected with
+ * GSR_EINVAL by the preprocess and the backward before any launch (coefficients past 16 are never read). */
 typedef struct gsr_set_scene {
   int V, P, degree, M, width, height, prefiltered;
   float scale_modifier;

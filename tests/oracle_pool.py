@@ -19,7 +19,8 @@ _SCENES = {}
 
 
 def scene_of(spec):
-    """spec = ("ball", n, sh_degree, seed) | ("sugar", subdiv, sh_degree, seed, colors): colors False keeps the
+    """spec = ("ball", n, sh_degree, seed) | ("gauss_backward", builder, *args) | ("sugar", subdiv, sh_degree, seed,
+    colors): colors False keeps the
     SH, True = SH2RGB(dc) as colors_precomp (the SuGaR normal renderer's pass 1), "normals" = the face normals as
     colors_precomp (its pass 2)."""
     key = tuple(spec)
@@ -28,6 +29,10 @@ def scene_of(spec):
 
         if spec[0] == "ball":
             s = gs.make_scene(spec[1], sh_degree=spec[2], seed=spec[3])
+        elif spec[0] == "gauss_backward":  # a constructed case of tests/gauss_backward_cases.py (its listed rows)
+            import gauss_backward_cases
+
+            s = gauss_backward_cases.scene_of_spec(spec)
         else:
             s = gs.make_sugar_scene(spec[1], sh_degree=spec[2], seed=spec[3])
             if spec[4] == "normals":

@@ -172,6 +172,24 @@ def test_argument_errors_without_gpu():
     assert chunks in backward(n_chunks=1, chunk_events=None)
     assert b"accumulate needs dL_dcov3D" in backward(accumulate=1, dL_dcov3D=None)
 
+    # SH rows wider than k_gauss_accum can stage in the CU's 160 KB of LDS (256 rows of sh_lds_stride(M) floats plus
+    # s_rl and s_wcnt: M = 50 asks for 160 016 bytes, M = 51 for 164 112) are rejected before any launch, by the
+    # preprocess and by the backward; M = 50 passes that check and fails the next one
+    import gauss_backward_cases as gc
+
+    assert gc.max_sh() == 50
+    wide = _C.SetScene.from_buffer_copy(scene)
+    wide.M = gc.max_sh() + 1
+    limit = b"largest SH width the per-Gaussian backward's LDS staging holds: M <= 50"
+    assert limit in err(lib.gsr_set_preprocess(wide, state, None, None))
+    assert limit in backward(wide)
+    nocounts = _C.SetState(radii=a, geom=a, binning=a, image=a, num_rendered=None)
+    fits = _C.SetScene.from_buffer_copy(scene)
+    fits.M = gc.max_sh()
+    assert b"null pointer argument" in err(lib.gsr_set_backward(fits, nocounts, _C.SetGrads(**g), None))
+    wide.colors_precomp, wide.shs = a, None  # (M is ignored without SHs)
+    assert b"null pointer argument" in err(lib.gsr_set_backward(wide, nocounts, _C.SetGrads(**dict(g, dL_dsh=None)), None))
+
     assert lib.gsr_set_backward_bytes(1, 10, K, 0) > 0
     for two_colors in (0, 1):
         assert lib.gsr_set_backward_bytes(0, 10, K, two_colors) == 0

@@ -91,6 +91,15 @@ static bool emit_spans_mode() {
   return on;
 }
 
+// SH rows wider than the per-Gaussian backward's LDS staging holds (gauss_backward_max_sh) are rejected by the
+// preprocess and the backward alike, before any launch
+static int check_sh_width(const gsr_set_scene& sc) {
+  if (sc.shs == nullptr || sc.M <= gauss_backward_max_sh()) return GSR_OK;
+  char lim[16];
+  snprintf(lim, sizeof(lim), "%d", gauss_backward_max_sh());
+  return fail(GSR_EINVAL, "M exceeds the largest SH width the per-Gaussian backward's LDS staging holds: M <= %s", lim);
+}
+
 static int effective_degree(int degree, int M) {
   // the reference reads sqrt(M)-1 coefficients at most (pred-normal pass quirk)
   int dm = (int)std::lround(std::sqrt((double)(M > 0 ? M : 1))) - 1;
@@ -276,6 +285,7 @@ static int set_preprocess(const gsr_set_scene* scene, const gsr_set_state* state
       (P > 0 && (sc.means3D == nullptr || sc.opacities == nullptr || state->radii == nullptr)))
     return null_argument();
   if (sc.shs != nullptr && sc.M <= 0) return invalid("M must be >= 1 with SHs");
+  if (check_sh_width(sc) != GSR_OK) return GSR_EINVAL;
   SetCams cams;
   if (set_cams(sc, cams) != GSR_OK) return GSR_EINVAL;
   for (int v = 0; v < V; ++v) {  // IEEE float division on the host = the device's correctly rounded one
@@ -500,6 +510,7 @@ static int check_backward(const gsr_set_scene& sc, const gsr_set_state& st, cons
   if (gr.n_chunks < 0 || gr.n_chunks > GSR_GRAD_CHUNKS_MAX || (gr.n_chunks > 0 && gr.chunk_events == nullptr))
     return invalid("bad gradient chunk request");
   if (sc.width <= 0 || sc.height <= 0) return invalid("bad sizes");
+  if (check_sh_width(sc) != GSR_OK) return GSR_EINVAL;
   if (sc.P == 0) return GSR_OK;
   if (st.num_rendered == nullptr || sc.bgs == nullptr || st.geom == nullptr || st.binning == nullptr ||
       st.image == nullptr || gr.work == nullptr || gr.dL_dcolor == nullptr || gr.dL_dmeans2D == nullptr ||

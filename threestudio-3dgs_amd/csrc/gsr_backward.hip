@@ -643,4 +643,14 @@ void launch_gauss_backward(const GaussBackwardArgs& a, ViewGradArgs va, const Ac
   hipLaunchKernelGGL(k_gauss_accum, dim3(div_up(n, 256)), dim3(256), lds, stream, a, b);
 }
 
+// Largest SH width M the per-Gaussian backward can launch: k_gauss_accum stages 256 rows of sh_lds_stride(M)
+// floats beside its s_rl and s_wcnt, and the CU has GSR_CU_LDS_BYTES.  (k_view_grad's request, the cut-offs up to
+// GSR_CUT_LDS_MAX plus s_list, and k_preprocess's, up to GSR_PRE_LDS_FLOATS, do not grow with M.)
+int gauss_backward_max_sh() {
+  const size_t fixed = 256 * sizeof(uint8_t) + 4 * sizeof(int);  // s_rl, s_wcnt
+  int M = 1;
+  while ((size_t)256 * sh_lds_stride(M + 1) * sizeof(float) + fixed <= GSR_CU_LDS_BYTES) ++M;
+  return M;
+}
+
 }  // namespace gsr

@@ -354,6 +354,10 @@ void launch_laplacian_forward(const MeshRegCall& c, float* lap, void* workspace,
 void launch_laplacian_backward(const MeshRegCall& c, const float* g_lap, float* dxyz, void* workspace,
                                hipStream_t stream);
 void launch_gauss_backward(const GaussBackwardArgs& a, ViewGradArgs va, const AccumArgs& b, hipStream_t stream);
+// LDS of one CU (gfx950), and the largest SH width whose k_gauss_accum staging fits it (gsr_backward.hip): the view-set
+// calls reject a larger M before any launch
+#define GSR_CU_LDS_BYTES (160 * 1024)
+int gauss_backward_max_sh();
 // Per-Gaussian backward of a timed view set (include/gsr.h gsr_set_timed_backward) — gsr_timed.hip.  The arrays are
 // the whole set's, (V, P, .), indexed by the set's view v0 + v like the geometry state.  scales_v / rotations_v null:
 // that parameter is shared (GaussBackwardArgs::scales / rotations) and its gradient is summed over the views into
